@@ -7,6 +7,12 @@ torchrun, one rank per GPU.  A "step" = one pass over the 8-query suite (each qu
 once like the reference's DataFrame, executed per step with results collected to host numpy
 columns, i.e. ``df.collect()``).  Weak scaling: every GPU holds SF=--sf (default 100) of
 synthetic TPC-H (random dictionary values), so N GPUs hold SF=100*N.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  ``--full`` adds the untimed
+passes reported alongside (``collect_ms``: every result column decoded to host objects;
+``kernels.shape_shared_geomean_ms``: the suite on the shape-shared kernels).  ``--dump-outputs DIR``
+writes the result columns of the last timed step as ``DIR/<query>__<column>.npy`` (the data is
+seeded, so two builds run with the same arguments can be compared output for output).
 """
 import argparse
 import json
@@ -24,11 +30,63 @@ os.environ.setdefault("SDO_JIT_SPECIALIZE", "sync")
 os.environ.setdefault("SDO_JIT_SPECIALIZE_AFTER", "1")
 
 BASELINE_GEOMEAN_MS = 5163.0  # reference Druid-backed geomean, 8 queries (SF10, 4x2-core)
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: all files together stay below this
 
 
 def log(*a):
     if int(os.environ.get("RANK", "0")) == 0:
         print(*a, file=sys.stderr, flush=True)
+
+
+def _result_columns(r):
+    """(name, column) of a timed run's result: a SQL statement's Batch or a spec query's QueryResult."""
+    if hasattr(r, "refs"):
+        return [(ref.name, r.cols[ref.rid]) for ref in r.refs]
+    return [(c, r.data[c]) for c in r.columns]
+
+
+def _as_float(col):
+    """A result column as float64: numbers as they are (NULL -> NaN), timestamps as epoch
+    nanoseconds, everything else (strings, decoded from their dictionary) as the CRC-32 of its text."""
+    import zlib
+
+    import numpy as np
+    import pandas as pd
+
+    if hasattr(col, "codes") and hasattr(col, "dictionary"):  # engine/columns.py DictColumn
+        col = col.to_numpy()
+    s = col if isinstance(col, pd.Series) else pd.Series(np.asarray(col))
+    if s.dtype.kind == "M":
+        return s.astype("int64").to_numpy(dtype=np.float64)
+    if pd.api.types.is_bool_dtype(s.dtype) or pd.api.types.is_numeric_dtype(s.dtype):
+        return s.to_numpy(dtype=np.float64, na_value=np.nan)
+    return np.array([np.nan if v is None or v is pd.NA else zlib.crc32(str(v).encode()) for v in s.tolist()],
+                    dtype=np.float64)
+
+
+def dump_outputs(outdir, results):
+    """Write every query's result columns as ``<query>__<column>.npy`` (float64).  Each query gets
+    an equal share of DUMP_MAX_BYTES; a larger result is cut to a fixed, seeded sample of its rows
+    (in result order)."""
+    import re
+
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(results))
+    for qi, (qname, r) in enumerate(results):
+        cols = _result_columns(r)
+        n = len(cols[0][1]) if cols else 0
+        keep = share // (8 * max(1, len(cols)))
+        idx = None
+        if n > keep:
+            idx = np.sort(np.random.default_rng(20260101).choice(n, size=keep, replace=False))
+        for ci, (cname, col) in enumerate(cols):
+            a = _as_float(col)
+            if idx is not None:
+                a = a[idx]
+            q, c = (re.sub(r"[^A-Za-z0-9]+", "_", x).strip("_") for x in (qname, cname))
+            np.save(os.path.join(outdir, f"{qi:02d}_{q}__{ci:02d}_{c}.npy"), a)
 
 
 def main():
@@ -46,13 +104,20 @@ def main():
                     help="tpch: the reference's 8-query TPC-H suite (headline); ssb: BASELINE config 4; "
                          "tpch22: the full 22-query TPC-H sweep over the flattened index (BASELINE config 2)")
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed passes reported alongside: collect_ms (every result column "
+                         "decoded to host objects) and the suite on the shape-shared kernels")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result columns of the last timed step as DIR/<query>__<column>.npy")
     # diagnostics (the JSON line then describes what was run)
     ap.add_argument("--only", default="", help="comma-separated subset of the suite's query names")
     ap.add_argument("--profile-rank", type=int, default=None, help="cProfile this rank's timed steps (stderr)")
     ap.add_argument("--keep-cache", action="store_true", help="keep the allocator cache of data generation")
-    ap.add_argument("--no-shape", action="store_true", help="skip the untimed shape-shared kernel pass")
+    ap.add_argument("--no-shape", action="store_true", help="(--full) skip the untimed shape-shared kernel pass")
     ap.add_argument("--per-rank", action="store_true", help="every rank's own per-query means")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU, started here (never from a process that touched the GPU)
         from spark_druid_olap_amd.utils.launch import spawn_ranks
@@ -155,6 +220,7 @@ def main():
     ctx.__enter__()
     lat = {name: [] for name, _ in queries}
     stats = {name: {} for name, _ in queries}
+    last = {}  # (--dump-outputs) every query's most recent timed result
     # the serving process's collector settings (server/gateway.py start): everything built so far --
     # shards, dictionaries, plans -- moves to the permanent generation and young collections come
     # less often, so a full collection does not walk it in the middle of a query
@@ -178,6 +244,8 @@ def main():
             a = time.perf_counter()
             r = pq.run()
             lat[name].append((time.perf_counter() - a) * 1e3)
+            if args.dump_outputs:
+                last[name] = r
             st = getattr(r, "stats", None) if args.verbose else None
             if st:
                 for k, v in st.items():
@@ -192,11 +260,14 @@ def main():
 
         prof.disable()
         pstats.Stats(prof, stream=sys.stderr).sort_stats("cumulative").print_stats(60)
-    # untimed, reported alongside: each query end to end INCLUDING host materialization of every result
+    if args.dump_outputs and world.rank == 0:  # (the answers are on rank 0)
+        dump_outputs(args.dump_outputs, [(n, last[n]) for n, _ in queries if last.get(n) is not None])
+    last.clear()
+    # (--full) untimed, reported alongside: each query end to end INCLUDING host materialization of every result
     # column (dictionary-coded strings decoded to Python objects, as the reference's df.collect() returns
     # them): the timed value leaves string columns dictionary-coded (engine/columns.py DictColumn)
     coll = {}
-    if args.mode == "sql":
+    if args.full and args.mode == "sql":
         with results_on_root(os.environ.get("SDO_RESULTS_ON_ROOT", "1") != "0"):
             for _ in range(max(2, min(args.steps, 3))):
                 for name, pq in queries:
@@ -208,8 +279,8 @@ def main():
                     coll.setdefault(name, []).append((time.perf_counter() - a) * 1e3)
                 world.barrier()
     shape_geo = None
-    if args.mode == "sql" and not only and not args.no_shape:
-        # untimed, reported alongside: the same suite on the shape-shared kernels a first-seen
+    if args.full and args.mode == "sql" and not only and not args.no_shape:
+        # (--full) untimed, reported alongside: the same suite on the shape-shared kernels a first-seen
         # parameterization runs (query constants read from the descriptor, no literal-specialized
         # code object) -- freshly planned statements with specialization switched off
         from spark_druid_olap_amd.engine import device_exec as DE
@@ -300,7 +371,7 @@ def main():
             "per_query_ms": {k: round(v, 4) for k, v in means.items()},
             "per_query_min_ms": {k: round(v, 4) for k, v in mins.items()},
             "per_query_max_ms": {k: round(v, 4) for k, v in maxs.items()},
-            # untimed: run + decode of every result column to host objects (df.collect()'s work)
+            # (--full) untimed: run + decode of every result column to host objects (df.collect()'s work)
             "collect_ms": {k: round(v, 4) for k, v in cmeans.items()} or None,
             "collect_geomean_ms": round(cgeo, 4) if cgeo is not None else None,
             "rows_per_gpu": int(nrows),
@@ -308,7 +379,7 @@ def main():
             # the timed steps run each prepared statement's literal-specialized kernel (compiled
             # synchronously at its first warmup run, SDO_JIT_SPECIALIZE=sync / _AFTER=1; a server
             # compiles it in the background for statements that repeat); the shape-shared kernels
-            # of a first-seen parameterization are reported untimed next to it
+            # of a first-seen parameterization are reported untimed next to it (--full)
             "kernels": {"timed": f"literal-specialized ({os.environ.get('SDO_JIT_SPECIALIZE')}, after "
                                  f"{os.environ.get('SDO_JIT_SPECIALIZE_AFTER')} run)",
                         "shape_shared_geomean_ms": round(shape_geo, 4) if shape_geo is not None else None},

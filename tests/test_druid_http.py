@@ -52,11 +52,9 @@ def test_coordinator_and_errors(srv):
                                                                      "dimensions": [], "intervals": []})
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/test/resources/zip_code.json.template"),
-                    reason="reference checkout not mounted")
 def test_overlord_index_task(srv):
-    ref = "/root/reference/src/test/resources"
-    text = open(f"{ref}/zip_code.json.template").read().replace(":DATA_DIR:", f"{ref}/zipCodes/sample")
+    zips = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "zipcodes")
+    text = open(f"{zips}/zip_code.json.template").read().replace(":DATA_DIR:", zips)
     ov = DruidOverlordClient("127.0.0.1", srv.port)
     tid = ov.submit_task(json.loads(text))
     st = ov.wait_until_task_completes(tid, timeout_s=30, poll_s=0.05)

@@ -1,7 +1,7 @@
 """Ingestion from the reference's own Druid index-task templates, then SQL over the result.
 
-* ``zip_codeAll.json.template`` + ``zipCodes/sample/zip_codes_states.csv`` (the reference's
-  QueryExtTest fixture): HLL / theta metrics, a spatial dimension, record_date time column.
+* ``zip_codeAll.json.template`` + ``zip_codes_states.csv`` (the reference's QueryExtTest fixture,
+  stored under ``tests/golden/zipcodes``): HLL / theta metrics, a spatial dimension, record_date time column.
 * ``tpch_index_task.json.template`` over a synthetic flattened TPC-H file (the real
   ``orderLineItemPartSupplierCustomer.small`` is not in the mirror): schemaless dimensions,
   JavaScript metrics, DAY query granularity with rollup, MONTH segments.
@@ -17,8 +17,12 @@ from spark_druid_olap_amd.query import spec as S
 from spark_druid_olap_amd.segment.ingest import IndexSpec, ingest
 from spark_druid_olap_amd.session import Session
 
+# the zip-code index tasks and their sample data are stored with the tests; the TPC-H index
+# template carries JavaScript aggregators (program text of the reference), so it is read from a
+# reference checkout where one is mounted
+ZIP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "zipcodes")
 REF = "/root/reference/src/test/resources"
-HAVE_REF = os.path.exists(f"{REF}/zip_codeAll.json.template")
+HAVE_REF = os.path.exists(f"{REF}/tpch_index_task.json.template")
 
 ZIP_INFOS = json.dumps([
     {"column": "city", "druidColumn": "city", "hllMetric": "unique_city", "sketchMetric": "city_sketch"},
@@ -30,14 +34,12 @@ ZIP_INFOS = json.dumps([
 
 @pytest.fixture(scope="module")
 def zsess():
-    if not HAVE_REF:
-        pytest.skip("reference checkout not mounted")
-    ds = ingest(f"{REF}/zip_codeAll.json.template", data_dir=f"{REF}/zipCodes/sample")
+    ds = ingest(f"{ZIP}/zip_codeAll.json.template", data_dir=ZIP)
     s = Session(engine=Engine(use_native=False))
     s.register_datasource(ds)
     s.sql(f"""CREATE TABLE zipCodesBase(record_date string, zip_code string, latitude double, longitude double,
       city string, state string, county string) USING com.databricks.spark.csv
-      OPTIONS (path "{REF}/zipCodes/sample/zip_codes_states.csv", header "false", delimiter ",")""")
+      OPTIONS (path "{ZIP}/zip_codes_states.csv", header "false", delimiter ",")""")
     s.sql(f"""CREATE TABLE zipCodesFull USING org.sparklinedata.druid OPTIONS (sourceDataframe "default.zipCodesBase",
       timeDimensionColumn "record_date", druidDatasource "zipCodesAll", columnInfos '{ZIP_INFOS}',
       nonAggregateQueryHandling "push_project_and_filters", allowTopNRewrite "true")""")

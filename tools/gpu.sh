@@ -7,7 +7,8 @@
 #   smoke              __graft_entry__.smoke()
 #   tests              pytest -m gpu (per-test thread timeout names a hung test)
 #   test:PATH          one GPU test file / node id
-#   bench              bench.py (SF, STEPS, WARMUP, MODEL env; extra args in BENCH_ARGS)
+#   bench              bench.py (SF, STEPS, WARMUP, MODEL env; extra args in BENCH_ARGS, e.g. --full for
+#                      the untimed collect_ms / shape-shared passes)
 #   rocprof            kernel trace + stats of the bench's timed steps -> gpurun_out/prof/summary.txt
 #   conc               tools/concurrency_bench.py (WORKLOAD fixed|varied|jmx, COALESCE, QPS, DUR, CLIENTS)
 #   probe              tools/sql_probe.py (PROBE_ARGS)
