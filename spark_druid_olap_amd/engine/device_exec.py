@@ -1482,7 +1482,7 @@ class PreparedEmit:
         ep = copy.copy(prog)
         ep.aops = [{"kind": D.A_ROWID, "col": -1, "expr": None, "filter": None, "slot": 0, "hll": -1}]
         ep.slots = [(D.S_SUM_I, 0)]
-        ep.nhll, ep.stored_hll, ep.thetas, ep.packed = 0, [], [], {}
+        ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.packed = 0, [], [], [], {}
         ep.presence_only = False
         self.prog = ep
         self.dev = prog.ds.device
@@ -1553,7 +1553,7 @@ def theta_producer_prog(prog: ScanProgram, cols: List[str]) -> ScanProgram:
     ep.aops = [{"kind": D.A_THETA, "col": ep.col(c), "expr": None, "filter": None, "slot": i, "hll": -1}
                for i, c in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(cols)
-    ep.nhll, ep.stored_hll, ep.thetas, ep.packed = 0, [], [], {}
+    ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.packed = 0, [], [], [], {}
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("theta: program not eligible")
@@ -1716,6 +1716,148 @@ class PreparedTheta:
                     self._mult[t0 + j] = int(mult[j * G:(j + 1) * G].max())
                     self.attempts[t0 + j] = attempt + 1
                     out[t0 + j] = _kmv(pj, ks[j])
+        finally:
+            PART_POOL.release(slab)
+        return out
+
+
+def quantile_producer_prog(prog: ScanProgram, cols: List[str]) -> ScanProgram:
+    """The scan program of a quantile producer: ``prog``'s filter, ranges and group key, one A_QVAL
+    aggregator (the value as an order-preserving u64, two record words) per distinct quantile
+    column, no other aggregator.  RuntimeError where it does not apply."""
+    import copy
+
+    from ..ops import jit as J
+
+    ds = prog.ds
+    for c in cols:
+        m = ds.metrics.get(c)
+        if m is None or m.sketch is not None or m.kind not in ("long", "double", "decimal"):
+            raise RuntimeError("quantile: fused only over long / decimal / double metrics")
+    ep = copy.copy(prog)
+    ep.pcols, ep.fcols, ep.section = list(prog.pcols), list(prog.fcols), "p"
+    ep.aops = [{"kind": D.A_QVAL, "col": ep.col(c), "expr": None, "filter": None, "slot": i, "hll": -1}
+               for i, c in enumerate(cols)]
+    ep.slots = [(D.S_SUM_I, 0)] * len(cols)
+    ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.packed = 0, [], [], [], {}
+    ep.presence_only = False
+    if not J.part_eligible(ep) or J.part_hashed(ep):
+        raise RuntimeError("quantile: program not eligible")
+    return ep
+
+
+QSEL_LDS_BINS = 64 * 1024 // 4   # u32 bins a workgroup's LDS histogram holds (the theta path's 64 KiB)
+QSEL_GLOBAL_BITS = 8             # digit width when the state rows' bins live in global memory
+QSEL_MAX_HIST_BYTES = 512 << 20
+
+
+class PreparedQuantile:
+    """``quantiles`` aggregators pushed into the scan: ONE JIT producer pass (ops/jit.py A_QVAL)
+    writes (u32 group key, ordered u64 value per distinct column) records of the selected rows into
+    its chunk regions, and the per-group radix rank select (ops/csrc/quantile.hip) resolves every
+    (group, rank target) in place, B value bits a pass -- no (key, row) pairs, no sort, no candidate
+    list, so duplicate-heavy metrics cost what distinct ones do.  One host read (the widest group's
+    value width: it fixes B and the pass count) precedes the result copy.  Long / decimal / double
+    metrics; G <= ``max_g``."""
+
+    def __init__(self, prog: ScanProgram, quantiles: list, max_g: int):
+        from .lower import lds_layout
+
+        ds = prog.ds
+        if prog.empty or not (0 < prog.G <= max_g):
+            raise RuntimeError("quantile: program not eligible")
+        self.cols = sorted({c for _, c, _, _ in quantiles})
+        ep = quantile_producer_prog(prog, self.cols)
+        self.prog, self.dev, self.G = ep, ds.device, int(prog.G)
+        self.jit = _jit_for(ep, D.M_PART, False, 1 << prog.hll_p)
+        if self.jit is None:
+            raise RuntimeError("quantile: no JIT kernel")
+        cache_off, wave_bytes, _, total = lds_layout(ep, 0, UNROLL, BLOCK // 64)
+        d = pack(ep, D.M_PART, 0, 0, 0, 0, 0, 0, 0, 0, 0, [], [], unroll=UNROLL, cache_off=cache_off,
+                 wave_bytes=wave_bytes)
+        self.nch = int(d[0]["total_chunks"])
+        self.grid = _grid(self.dev, self.nch, self.jit.lay.total, self.jit)
+        self.rw = 1 + 2 * len(self.cols)
+        cap = self.nch * D.CHUNK_ROWS
+        if cap * self.rw >= (1 << 32):
+            raise RuntimeError("quantile: shard too large for u32 offsets")
+        self.words = max(1, cap * self.rw)
+        self.seg_lo = (torch.arange(self.nch, dtype=torch.int64) * D.CHUNK_ROWS).to(torch.int32).to(self.dev)
+        self._d = d
+        # per aggregator: (value word offset, fractions, interpolate, is double, decimal scale)
+        self.sel = []
+        for _, c, fr, interp in quantiles:
+            m = ds.metrics[c]
+            nr = self.G * len(fr) * (2 if interp else 1)
+            if (nr << (QSEL_GLOBAL_BITS if nr * 16 > QSEL_LDS_BINS else 4)) * 4 > QSEL_MAX_HIST_BYTES:
+                raise RuntimeError("quantile: too many (group, rank) rows")
+            self.sel.append((1 + 2 * self.cols.index(c), tuple(fr), bool(interp), m.kind == "double",
+                             int(m.scale) if m.kind == "decimal" else 0))
+        self.plan = []  # (per aggregator of the last run: value width W, digit bits B, levels)
+
+    @staticmethod
+    def digit_bits(rows: int, width: int) -> int:
+        """Digit width for ``rows`` state rows and a ``width``-bit widest group: the widest B in
+        4..12 whose [rows][2^B] bins fit a workgroup's LDS, narrowed to ceil(width / levels) (as
+        many passes, fewer bins to clear / scan / flush); rows beyond LDS: 8 bits, global bins."""
+        if rows * 16 > QSEL_LDS_BINS:
+            return QSEL_GLOBAL_BITS
+        fit = min(12, int(math.floor(math.log2(QSEL_LDS_BINS // rows))))
+        levels = max(1, -(-width // fit))
+        return max(4, min(fit, -(-width // levels)))
+
+    def select(self) -> list:
+        """Per aggregator its values [G, fractions] (host): float64 (interpolated, double and
+        decimal columns) or int64 (elements of a long column).  Rows of empty groups hold zeros."""
+        nat, st = native.load(), native._stream(self.dev)
+        dev, G = self.dev, self.G
+        i32, i64 = torch.int32, torch.int64
+        pend = torch.empty(max(1, self.nch), dtype=i32, device=dev)
+        slab = PART_POOL.acquire(dev, self.words)
+        out, self.plan = [], []
+        try:
+            d = self._d.copy()
+            d[0]["part_recs"] = slab.recs1.data_ptr()
+            d[0]["part_counts"] = pend.data_ptr()
+            desc = _upload(d.view(np.uint8), dev)
+            nat.module_launch(self.jit.handle, desc.data_ptr(), int(self.grid), BLOCK, int(self.jit.lay.total), st)
+            # count / min / max / width depend on the column only: one stats pass per distinct column,
+            # their widest-group widths read together (the only sync before the result copies)
+            stats = {}
+            for voff in sorted({s[0] for s in self.sel}):
+                cnt = torch.empty(G, dtype=i32, device=dev)
+                mn = torch.empty(G, dtype=i64, device=dev)
+                mx = torch.empty(G, dtype=i64, device=dev)
+                width = torch.empty(G, dtype=i32, device=dev)
+                wmax = torch.empty(1, dtype=i32, device=dev)
+                nat.qsel_stats(slab.recs1.data_ptr(), self.rw, voff, self.seg_lo.data_ptr(), pend.data_ptr(),
+                               self.nch, G, cnt.data_ptr(), mn.data_ptr(), mx.data_ptr(), width.data_ptr(),
+                               wmax.data_ptr(), st)
+                stats[voff] = [cnt, mn, mx, width, wmax]
+            for st_, w in zip(stats.values(), torch.cat([s[4] for s in stats.values()]).cpu().tolist()):
+                st_[4] = int(w)
+            for voff, fr, interp, is_f64, scale in self.sel:
+                T = len(fr) * (2 if interp else 1)
+                cnt, mn, mx, width, W = stats[voff]
+                regions = (slab.recs1.data_ptr(), self.rw, voff, self.seg_lo.data_ptr(), pend.data_ptr(), self.nch, G)
+                frac = torch.tensor(fr, dtype=torch.float64).to(dev)
+                B = self.digit_bits(G * T, W)
+                levels = -(-W // B)
+                self.plan.append((W, B, levels))
+                prefix = torch.empty(G * T, dtype=i64, device=dev)
+                rank = torch.empty(G * T, dtype=i64, device=dev)
+                hist = torch.empty(max(1, (G * T) << B) if levels else 1, dtype=i32, device=dev)
+                res = torch.empty((G, len(fr)), dtype=i64, device=dev)
+                div = float(10 ** scale) if interp else 1.0
+                nat.qsel_select(*regions, T, B, 1 if interp else 0, cnt.data_ptr(), mn.data_ptr(), mx.data_ptr(),
+                                width.data_ptr(), prefix.data_ptr(), rank.data_ptr(), hist.data_ptr(),
+                                frac.data_ptr(), levels, len(fr), 1 if is_f64 else 0, div, res.data_ptr(), st)
+                h = res.cpu().numpy()
+                if interp or is_f64:
+                    h = h.view(np.float64)
+                elif scale:
+                    h = h.astype(np.float64) / (10.0 ** scale)
+                out.append(h)
         finally:
             PART_POOL.release(slab)
         return out

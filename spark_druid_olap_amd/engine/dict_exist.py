@@ -85,7 +85,7 @@ def plan(prog) -> Optional[Tuple[str, Tuple[str, ...]]]:
 
 def _plan(prog):
     ds = prog.ds
-    if prog.empty or not prog.presence_only or prog.nhll or prog.stored_hll or prog.thetas:
+    if prog.empty or not prog.presence_only or prog.nhll or prog.stored_hll or prog.needs_rows:
         return None, "not existence-only"
     if len(prog.keys) != 1 or prog.nslots != 1 or getattr(ds, "fd_source", None) is not None:
         return None, "not one key"

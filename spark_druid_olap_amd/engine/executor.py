@@ -96,7 +96,9 @@ class QueryResult:
     def to_pandas(self):
         import pandas as pd
 
-        return pd.DataFrame({c: materialize(self.data[c]) for c in self.columns}, columns=self.columns)
+        data = {c: materialize(self.data[c]) for c in self.columns}
+        # (a quantiles column is [groups, fractions]: one array per row)
+        return pd.DataFrame({c: (list(v) if v.ndim == 2 else v) for c, v in data.items()}, columns=self.columns)
 
     def sorted_rows(self) -> List[tuple]:
         return sorted(self.rows(), key=lambda r: tuple((x is None, str(x)) for x in r))
@@ -128,7 +130,7 @@ class _SmallDenseRunner:
         _, prog, prep = pq.scans[0]
         if not isinstance(prep, PreparedScan) or prep.mode != D.M_DENSE_LDS or prep.touch or prep.pres_bytes:
             return None
-        if prog.empty or prog.stored_hll or prog.thetas or getattr(prog, "derived_aggs", None) or \
+        if prog.empty or prog.stored_hll or prog.needs_rows or getattr(prog, "derived_aggs", None) or \
                 any(kc.collapse for kc in prog.keys) or pq._dict_exist_plan(prog) is not None:
             return None
         from .partials import SMALL_DENSE_WORDS
@@ -213,6 +215,8 @@ class PreparedQuery:
                 dims = [qs.dimension]
             prog = self.low.lower_aggregate(qs.intervals, qs.filter, dims, qs.granularity, qs.aggregations)
             self._full_prog = prog
+            if prog.quantiles:
+                _check_quantile_refs(qs, {name for name, _, _, _ in prog.quantiles})
             # grouped on the shard key across several ranks: scan this shard's key window only
             self.window = shard_window(prog, ds, self.world)
             if self.window is not None:
@@ -486,6 +490,7 @@ class PreparedQuery:
             t3 = time.perf_counter()
             with T.span("sdo.post"):
                 self._theta(self._full_prog, cols)
+                self._quantile(self._full_prog, cols)
                 res = self._post(prog, cols)
             t4 = time.perf_counter()
             res.stats.update(scan_ms=(t1 - t0) * 1e3, merge_ms=(t2 - t1) * 1e3, finalize_ms=(t3 - t2) * 1e3,
@@ -509,7 +514,7 @@ class PreparedQuery:
                 or not self.scans:
             return False
         prog = self.scans[0][1]
-        if getattr(self._full_prog, "thetas", None) or any(kc.collapse for kc in prog.keys):
+        if self._full_prog.needs_rows or any(kc.collapse for kc in prog.keys):
             return False
         return min(float(prog.G), float(getattr(prog, "est_rows", prog.G) or prog.G)) >= STREAM_MIN_GROUPS
 
@@ -740,7 +745,7 @@ class PreparedQuery:
         from ..ops import desc as D_
 
         h = getattr(self.qs, "having", None)
-        if h is None or self.qs.queryType != "groupBy" or prog.thetas or any(kc.collapse for kc in prog.keys):
+        if h is None or self.qs.queryType != "groupBy" or prog.needs_rows or any(kc.collapse for kc in prog.keys):
             return False
         if prep is None or getattr(prep, "mode", None) != D_.M_PART or len(self.scans) != 1:
             return False
@@ -777,7 +782,7 @@ class PreparedQuery:
         from ..ops import desc as D_
 
         qs = self.qs
-        if prog.thetas or any(kc.collapse for kc in prog.keys):
+        if prog.needs_rows or any(kc.collapse for kc in prog.keys):
             return False
         if prep is None or getattr(prep, "mode", None) != D_.M_PART or len(self.scans) != 1:
             return False
@@ -808,7 +813,7 @@ class PreparedQuery:
         shipped and decoded.  Returns (partials, applied); the host re-applies the same spec in
         ``_post`` (idempotent).  Specs over sketches / post-aggregations stay on the host."""
         h = getattr(self.qs, "having", None)
-        if h is None or self.qs.queryType != "groupBy" or prog.thetas or any(kc.collapse for kc in prog.keys):
+        if h is None or self.qs.queryType != "groupBy" or prog.needs_rows or any(kc.collapse for kc in prog.keys):
             return part, h is None
         if self._having_fused and part.kind == "sparse" and not part.scattered:
             # the partitioned aggregation already emitted only the groups passing it: a second pass
@@ -876,7 +881,7 @@ class PreparedQuery:
         not be applied here first, when a metric value is NaN (Spark sorts NaN last), or when the
         partition space is too large for a table."""
         pe = getattr(self, "partition_extreme", None)
-        if not pe or self.qs.queryType != "groupBy" or prog.thetas or any(kc.collapse for kc in prog.keys):
+        if not pe or self.qs.queryType != "groupBy" or prog.needs_rows or any(kc.collapse for kc in prog.keys):
             return part
         pnames, metric, asc = pe
         agg = next((a for a in prog.aggs if a.name == metric), None)
@@ -965,7 +970,7 @@ class PreparedQuery:
             name, desc, limit = qs.metric.metric, True, int(qs.threshold)
         else:
             return part
-        if limit <= 0 or part.rows <= max(4 * limit, 4096) or prog.thetas or any(kc.collapse for kc in prog.keys):
+        if limit <= 0 or part.rows <= max(4 * limit, 4096) or prog.needs_rows or any(kc.collapse for kc in prog.keys):
             return part
         agg = next((a for a in prog.aggs if a.name == name), None)
         if agg is None or agg.slot < 0 or agg.kind not in ("count", "sum_i", "sum_f", "min_i", "max_i"):
@@ -1083,6 +1088,75 @@ class PreparedQuery:
             allp = torch.cat(got)
             return _kmv(_sorted_unique_pairs(allp[:, 0], allp[:, 1]), size)
         return pairs[:0]
+
+    # ------------------------------------------------------------------ order statistics
+    def _quantile(self, prog: ScanProgram, cols: Dict[str, np.ndarray]) -> None:
+        """``quantiles`` aggregators: per group and fraction the exact order statistic of the
+        selected rows' values, a result column [groups, fractions].  On the device the radix rank
+        select answers (engine/device_exec.py PreparedQuantile); everywhere else -- CPU, no native
+        code, programs or columns the select does not take -- the (group, value) pairs of the
+        selected rows are sorted with torch."""
+        if not prog.quantiles:
+            return
+        gid_order = np.asarray(cols["__gid__"], dtype=np.int64)
+        fused = self._quantile_fused(prog)
+        if fused is not None:
+            for (name, _, _, _), res in zip(prog.quantiles, fused):
+                cols[name] = res[np.clip(gid_order, 0, max(0, len(res) - 1))]
+            return
+        from ..ops.reference import _rows, compute_keys, eval_bexpr
+        from .lower import column_tensor, dim_numeric_lut
+
+        ds = self.ds
+        dev = ds.device
+        keys = rows = None
+        if not prog.empty and dev.type == "cuda" and self.engine.use_native:
+            try:
+                em = self.__dict__.get("_emit")
+                if em is None:
+                    from .device_exec import PreparedEmit
+
+                    em = self._emit = PreparedEmit(prog)
+                keys, rows = em.run()
+            except RuntimeError:
+                keys = rows = None
+        if rows is None:
+            rows = _rows(prog) if not prog.empty else torch.zeros(0, dtype=torch.int64, device=dev)
+            if rows.numel():
+                rows = rows[eval_bexpr(prog, prog.bexpr, rows)]
+            keys = compute_keys(prog, rows)
+        for name, col, fr, interp in prog.quantiles:
+            m = ds.metrics.get(col)
+            v = column_tensor(ds, col)[rows]
+            if m is None:  # a dimension: its dictionary's numeric values
+                v = dim_numeric_lut(ds, col)[v.to(torch.int64)]
+            v = v.to(torch.float64 if v.dtype.is_floating_point else torch.int64)
+            scale = int(m.scale) if m is not None and m.kind == "decimal" else 0
+            gids, res = _sorted_quantiles(keys, v, fr, interp, scale)
+            at = np.searchsorted(gids, gid_order)
+            cols[name] = res[np.clip(at, 0, max(0, len(res) - 1))] if len(res) else \
+                np.zeros((len(gid_order), len(fr)), dtype=res.dtype)
+
+    def _quantile_fused(self, prog: ScanProgram) -> Optional[list]:
+        """Per quantiles aggregator its values [G, fractions] from the device select, or None where
+        it does not apply (CPU, dimensions, wide key spaces, an empty shard, a failed run)."""
+        if prog.empty or self.ds.device.type != "cuda" or not self.engine.use_native:
+            return None
+        qp = self.__dict__.get("_quantile_prep")
+        if qp is None:
+            try:
+                from .device_exec import PreparedQuantile
+
+                qp = PreparedQuantile(prog, prog.quantiles, QUANTILE_SELECT_MAX_G)
+            except RuntimeError:
+                qp = False
+            self._quantile_prep = qp
+        if qp is False:
+            return None
+        try:
+            return qp.select()
+        except RuntimeError:
+            return None
 
     # ------------------------------------------------------------------ post processing
     def _post(self, prog: ScanProgram, cols: Dict[str, np.ndarray]) -> QueryResult:
@@ -1314,7 +1388,7 @@ def shard_window(prog: ScanProgram, ds: DataSource, world: World) -> Optional[Sh
     import copy
 
     # (everything up to the agreement below depends on the plan only -- identical on every rank)
-    if world is None or not world.distributed or not ds.shard_key or prog.thetas:
+    if world is None or not world.distributed or not ds.shard_key or prog.needs_rows:
         return None
     idx = next((i for i, kc in enumerate(prog.keys)
                 if kc.kind == D.K_ID and kc.col == ds.shard_key and kc.orig is None and kc.base == 0), None)
@@ -1447,6 +1521,65 @@ def _kmv_estimates(pairs: torch.Tensor, k: int, gid_order: np.ndarray) -> np.nda
 
 
 THETA_SELECT_MAX_G = 4096  # groups the device radix select handles (histogram G x 2^bits u32)
+QUANTILE_SELECT_MAX_G = 1 << 16  # groups the device rank select handles (state rows G x targets)
+
+
+def _check_quantile_refs(qs, names) -> None:
+    """A quantiles column holds one value per fraction: HAVING, limitSpec ordering, a topN metric or
+    a post-aggregation cannot read it as a number (SQL projects the fractions out first)."""
+    import dataclasses
+
+    def walk(x):
+        if isinstance(x, str):
+            if x in names:
+                raise LoweringError(f"the quantiles aggregator {x!r} holds one value per fraction: it cannot be "
+                                    "read by having / limitSpec / metric / postAggregations")
+        elif isinstance(x, (list, tuple)):
+            for y in x:
+                walk(y)
+        elif dataclasses.is_dataclass(x):
+            for f in dataclasses.fields(x):
+                walk(getattr(x, f.name))
+
+    for attr in ("having", "limitSpec", "metric", "postAggregations"):
+        walk(getattr(qs, attr, None))
+
+
+def _sorted_quantiles(g: torch.Tensor, v: torch.Tensor, fractions, interpolate: bool, scale: int):
+    """Order statistics by sorting: (group ids ascending, values [groups, fractions]) of the
+    (group, value) pairs -- ``v`` int64 (a decimal's unscaled digits) or float64.  Interpolated:
+    lo + (hi - lo) * (pos - floor(pos)) at pos = p (n-1), float64, a decimal's scale applied to lo
+    and hi; else the element at rank max(0, ceil(p n) - 1) (a decimal as float64)."""
+    nf = len(fractions)
+    is_f = v.dtype.is_floating_point
+    if not g.numel():
+        return np.zeros(0, dtype=np.int64), np.zeros((0, nf), dtype=np.float64 if (interpolate or is_f or scale) else np.int64)
+    o1 = torch.sort(v, stable=True).indices
+    o2 = torch.sort(g[o1], stable=True).indices
+    order = o1[o2]
+    gs, vs = g[order], v[order]
+    gids, cnt = torch.unique_consecutive(gs, return_counts=True)
+    start = torch.cumsum(cnt, 0) - cnt
+    n = cnt.to(torch.float64)
+    p = torch.tensor(list(fractions), dtype=torch.float64, device=v.device)
+
+    def value(x):
+        x = x.to(torch.float64)
+        return x / (10.0 ** scale) if scale else x
+
+    if interpolate:
+        pos = p[None, :] * (n[:, None] - 1.0)
+        lo_r = torch.floor(pos)
+        lo = value(vs[start[:, None] + lo_r.to(torch.int64)])
+        hi = value(vs[start[:, None] + torch.ceil(pos).to(torch.int64)])
+        gm = pos - lo_r  # (anchored at the nearer rank: no cancellation error across a sign change)
+        res = torch.where(gm >= 0.5, hi - (hi - lo) * (1.0 - gm), lo + (hi - lo) * gm)
+    else:
+        r = torch.clamp(torch.ceil(p[None, :] * n[:, None]) - 1.0, min=0.0).to(torch.int64)
+        res = vs[start[:, None] + r]
+        if scale:
+            res = value(res)
+    return gids.cpu().numpy(), res.cpu().numpy()
 
 
 def kmv_select(g: torch.Tensor, h: torch.Tensor, k: int, G: int) -> torch.Tensor:
@@ -1763,7 +1896,7 @@ def execute_grouping_sets(engine, specs, ds, out_types=None) -> Optional[List[Qu
             cache.clear()
         cache[key] = pq
     fine = pq._full_prog
-    if fine.thetas or fine.stored_hll or fine.derived_aggs or any(kc.collapse for kc in fine.keys):
+    if fine.needs_rows or fine.stored_hll or fine.derived_aggs or any(kc.collapse for kc in fine.keys):
         return None
     t0 = time.perf_counter()
     root_only = engine.world.distributed and root_only_results()

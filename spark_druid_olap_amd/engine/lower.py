@@ -330,7 +330,7 @@ class KeyComp:
 @dataclass
 class AggOut:
     name: str
-    kind: str                     # count|sum_i|sum_f|sum_fx|min_i|max_i|min_f|max_f|hll|theta
+    kind: str                     # count|sum_i|sum_f|sum_fx|min_i|max_i|min_f|max_f|hll|theta|quantile
     slot: int = -1
     slot2: int = -1               # sum_fx: fraction slot (value = slot + slot2 * 2^-32)
     hll_index: int = -1
@@ -367,6 +367,8 @@ class ScanProgram:
     agg_filters: List[Any] = field(default_factory=list) # per aop bexpr or None
     keepalive: List[torch.Tensor] = field(default_factory=list)
     thetas: List[Tuple[str, str, int]] = field(default_factory=list)  # (name, column, size)
+    # order statistics: (name, column, fractions, interpolate)
+    quantiles: List[Tuple[str, str, Tuple[float, ...], bool]] = field(default_factory=list)
     luts: Dict[str, torch.Tensor] = field(default_factory=dict)       # dim -> f64 value per dictionary id
     lut_ptrs: Dict[float, torch.Tensor] = field(default_factory=dict)  # E_LUT operand -> its table
     # grouping keys functionally determined by a packed key: (key, index of determinant in keys,
@@ -381,6 +383,13 @@ class ScanProgram:
     # hyperUnique over rolled-up sketch metrics: (output name, metric, aggregator filter or None);
     # their registers follow the scan's ``nhll`` query-time HLL blocks in Partials.hll
     stored_hll: List[Tuple[str, str, Any]] = field(default_factory=list)
+
+    @property
+    def needs_rows(self) -> bool:
+        """Some aggregator reads the selected rows themselves (theta KMV, order statistics), not an
+        accumulator: strategies that keep only accumulators decline, the executor answers it after
+        the scan (engine/executor.py _theta / _quantile)."""
+        return bool(self.thetas or self.quantiles)
 
     @property
     def nhll_total(self) -> int:
@@ -1277,6 +1286,22 @@ class Lowerer:
                 raise LoweringError(f"thetaSketch over the {m.sketch.kind} sketch metric {a.fieldName!r}")
             prog.thetas.append((a.name, a.fieldName, int(a.size)))
             prog.aggs.append(AggOut(a.name, "theta", combine="theta"))
+            return
+        if isinstance(a, S.QuantilesAggregationSpec):
+            if self.world is not None and self.world.distributed:
+                # (every rank would select over its own shard: the per-level histograms are not
+                # reduced across ranks yet -- the SQL layer answers such statements on the host)
+                raise LoweringError("quantiles aggregators are not answered across ranks")
+            m = ds.metrics.get(a.fieldName)
+            if a.fieldName not in ds.dims and m is None:
+                raise LoweringError(f"quantiles over unknown column {a.fieldName!r}")
+            if m is not None and (m.sketch is not None or m.kind not in ("long", "double", "decimal")):
+                raise LoweringError(f"quantiles over the sketch metric {a.fieldName!r}")
+            fr = tuple(float(f) for f in a.fractions)
+            if not fr or any(not (0.0 <= f <= 1.0) for f in fr):
+                raise LoweringError("quantiles: fractions must lie in [0, 1]")
+            prog.quantiles.append((a.name, a.fieldName, fr, bool(a.interpolate)))
+            prog.aggs.append(AggOut(a.name, "quantile", combine="quantile"))
             return
         raise LoweringError(f"unsupported aggregator {type(a).__name__}")
 

@@ -72,7 +72,7 @@ def device_columns(pq) -> Tuple[Dict[str, DeviceColumn], int]:
         torch.cuda.synchronize()
         print(f"[nested] inner scan+merge {(time.perf_counter() - t0) * 1e3:.2f} ms mode="
               f"{getattr(pq.scans[0][2], 'mode', None)} G={prog.G} rows={part.rows}", flush=True)
-    if prog.thetas or any(kc.collapse for kc in prog.keys):
+    if prog.needs_rows or any(kc.collapse for kc in prog.keys):
         raise LoweringError("nested query over theta sketches / non-injective keys")
     if part.kind == "dense":
         part = part.compact()

@@ -258,7 +258,7 @@ def _agg_outputs_dev(prog, acc: torch.Tensor, skip) -> Dict[str, torch.Tensor]:
     """Final aggregator columns on the device (same values as finalize's host conversions)."""
     out = {}
     for a in prog.aggs:
-        if a.name in skip or a.slot < 0 or a.kind in ("hll", "theta"):
+        if a.name in skip or a.slot < 0 or a.kind in ("hll", "theta", "quantile"):
             continue
         col = acc[:, a.slot]
         if a.kind == "count":
@@ -376,7 +376,7 @@ def _native_sparse(prog, parts: Partials, out_types, want_gid: bool):
         order.append(("dag", j))
     derived_names = {a.name for a, _, _ in getattr(prog, "derived_aggs", ())}
     for a in prog.aggs:
-        if a.name in derived_names or a.slot < 0 or a.kind in ("hll", "theta"):
+        if a.name in derived_names or a.slot < 0 or a.kind in ("hll", "theta", "quantile"):
             continue
         if a.kind == "count":
             sp = (1, 2, 0, a.slot, 1, 1, 0, 0, 0, 0.0)
@@ -487,7 +487,7 @@ def finalize(prog, parts: Partials, out_types: Optional[Dict[str, str]] = None,
     their dictionary's width, numeric dictionary keys as final SQL-typed values when ``out_types``
     (output name -> SQL type, from the SQL layer) asks for them, constant keys not at all, and only
     the accumulator slots an output reads."""
-    want_gid = bool(getattr(prog, "thetas", None))
+    want_gid = bool(getattr(prog, "needs_rows", False))
     collapse = any(kc.collapse for kc in prog.keys)
     typed: Dict[int, object] = {}
     est_host: List[np.ndarray] = []
@@ -716,7 +716,7 @@ def finalize(prog, parts: Partials, out_types: Optional[Dict[str, str]] = None,
                 cols[a.name] = est_host[a.hll_index]
             else:
                 cols[a.name] = hll_estimates(hll_d[a.hll_index], prog.hll_p) if R else np.zeros(0)
-        elif a.kind == "theta":
+        elif a.kind in ("theta", "quantile"):
             pass  # filled by the executor
     # group count of the result (only its length is read downstream)
     cols["__rows__"] = acc_cols[0] if 0 in acc_cols else np.zeros(R, dtype=np.int8)

@@ -21,6 +21,7 @@
 #include <vector>
 #include "scan_desc.h"
 #include "post_scan.h"
+#include "quantile.h"
 
 namespace sdo {
 template <int U>
@@ -88,6 +89,18 @@ __global__ void theta_hist_kernel(const int64_t* g, const int64_t* h, int64_t n,
 __global__ void theta_thresh_kernel(const uint32_t* hist, int bits, const int64_t* target, int64_t* bound);
 __global__ void theta_filter_kernel(const int64_t* g, const int64_t* h, int64_t n, const int64_t* bound,
                                     int64_t* out_g, int64_t* out_h, unsigned long long* count, int64_t cap);
+// quantile.hip (QselState: quantile.h)
+__global__ void qsel_init_kernel(uint32_t* cnt, uint64_t* mn, uint64_t* mx, int G, uint32_t* wmax);
+__global__ void qsel_clear_kernel(uint32_t* p, int64_t n);
+__global__ void qsel_stats_regions_kernel(const uint32_t* recs, int rw, int voff, const uint32_t* seg_lo,
+                                          const uint32_t* seg_hi, int64_t nseg, int G, int GL, uint32_t* cnt,
+                                          uint64_t* mn, uint64_t* mx);
+__global__ void qsel_width_kernel(const uint32_t* cnt, const uint64_t* mn, const uint64_t* mx, int G, uint32_t* width,
+                                  uint32_t* wmax);
+__global__ void qsel_hist_regions_kernel(const uint32_t* recs, int rw, int voff, const uint32_t* seg_lo,
+                                         const uint32_t* seg_hi, int64_t nseg, QselState s, int level, int use_lds);
+__global__ void qsel_pick_kernel(QselState s, int level);
+__global__ void qsel_final_kernel(QselState s, int nfrac, int is_f64, double div, uint64_t* out);
 // p2p.hip (P2PArgs: p2p.h)
 __global__ void p2p_merge_kernel(P2PArgs a);
 }  // namespace sdo
@@ -865,6 +878,77 @@ static void theta_select_regions(uint64_t recs, int rw, int hoff, uint64_t seg_l
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-group radix rank select over a quantile producer's chunk-region records (quantile.hip):
+// record = u32 group key, then 2 words of order-preserving u64 value per quantile column; the
+// selected column's value starts at word `voff`.
+static constexpr int64_t QSEL_LDS = 64 * 1024;  // per-workgroup table budget (the theta histogram's)
+
+static void qsel_check(int rw, int voff, int64_t G) {
+  if (G <= 0 || G > (1 << 20)) throw std::invalid_argument("qsel: 1..2^20 groups");
+  if (rw < 3 || voff < 1 || voff + 2 > rw) throw std::invalid_argument("qsel: record layout");
+}
+
+// Pass 1: per-group count / min / max, the groups' value widths and the largest of them (`wmax`,
+// the host's one read: it fixes the digit width and the number of levels).
+static void qsel_stats(uint64_t recs, int rw, int voff, uint64_t seg_lo, uint64_t seg_hi, int64_t nseg, int64_t G,
+                       uint64_t cnt, uint64_t mn, uint64_t mx, uint64_t width, uint64_t wmax, uint64_t stream) {
+  qsel_check(rw, voff, G);
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned gg = (unsigned)((G + 255) / 256);
+  hipLaunchKernelGGL(sdo::qsel_init_kernel, dim3(gg), dim3(256), 0, s, (uint32_t*)cnt, (uint64_t*)mn, (uint64_t*)mx,
+                     (int)G, (uint32_t*)wmax);
+  check(hipGetLastError(), "qsel_init_kernel launch");
+  if (nseg > 0) {
+    const int GL = (int)std::min<int64_t>(G, QSEL_LDS / 20);  // (u32 count + u64 min + u64 max a group)
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(nseg, 1024));
+    hipLaunchKernelGGL(sdo::qsel_stats_regions_kernel, dim3(grid), dim3(256), (size_t)GL * 20, s,
+                       (const uint32_t*)recs, rw, voff, (const uint32_t*)seg_lo, (const uint32_t*)seg_hi, nseg, (int)G,
+                       GL, (uint32_t*)cnt, (uint64_t*)mn, (uint64_t*)mx);
+    check(hipGetLastError(), "qsel_stats_regions_kernel launch");
+  }
+  hipLaunchKernelGGL(sdo::qsel_width_kernel, dim3(gg), dim3(256), 0, s, (const uint32_t*)cnt, (const uint64_t*)mn,
+                     (const uint64_t*)mx, (int)G, (uint32_t*)width, (uint32_t*)wmax);
+  check(hipGetLastError(), "qsel_width_kernel launch");
+}
+
+// Passes 2..: `levels` rounds of (clear bins, histogram, pick), then the result [G][nfrac].  The
+// bins are per-workgroup LDS when the level's rows fit the budget (level 0 has G rows, later
+// levels G x T), else global.
+static void qsel_select(uint64_t recs, int rw, int voff, uint64_t seg_lo, uint64_t seg_hi, int64_t nseg, int64_t G,
+                        int T, int B, int interpolate, uint64_t cnt, uint64_t mn, uint64_t mx, uint64_t width,
+                        uint64_t prefix, uint64_t rank, uint64_t hist, uint64_t frac, int levels, int nfrac,
+                        int is_f64, double div, uint64_t out, uint64_t stream) {
+  qsel_check(rw, voff, G);
+  if (B < 4 || B > 12) throw std::invalid_argument("qsel_select: 4..12 digit bits");
+  if (T < 1 || T != nfrac * (interpolate ? 2 : 1)) throw std::invalid_argument("qsel_select: targets per group");
+  if (levels < 0 || levels * B >= 64 + B) throw std::invalid_argument("qsel_select: levels");
+  if (G * T > (int64_t)1 << 22) throw std::invalid_argument("qsel_select: too many state rows");
+  hipStream_t s = (hipStream_t)stream;
+  sdo::QselState st{(int)G, T, B, interpolate, (uint32_t*)cnt, (uint64_t*)mn, (uint64_t*)mx, (uint32_t*)width,
+                    (uint64_t*)prefix, (uint64_t*)rank, (uint32_t*)hist, (const double*)frac};
+  for (int level = 0; level < levels; ++level) {
+    const int64_t rows = level == 0 ? G : G * T;
+    const int64_t nb = rows << B;
+    hipLaunchKernelGGL(sdo::qsel_clear_kernel, dim3(grid_for(nb, 256, 4096)), dim3(256), 0, s, (uint32_t*)hist, nb);
+    check(hipGetLastError(), "qsel_clear_kernel launch");
+    if (nseg > 0) {
+      const int use_lds = nb * 4 <= QSEL_LDS ? 1 : 0;
+      // (LDS bins: fewer, longer-running workgroups -- each flushes its bins onto the same addresses)
+      const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(nseg, use_lds ? 1024 : 4096));
+      hipLaunchKernelGGL(sdo::qsel_hist_regions_kernel, dim3(grid), dim3(256), use_lds ? (size_t)nb * 4 : 0, s,
+                         (const uint32_t*)recs, rw, voff, (const uint32_t*)seg_lo, (const uint32_t*)seg_hi, nseg, st,
+                         level, use_lds);
+      check(hipGetLastError(), "qsel_hist_regions_kernel launch");
+    }
+    hipLaunchKernelGGL(sdo::qsel_pick_kernel, dim3((unsigned)(G * T)), dim3(256), 0, s, st, level);
+    check(hipGetLastError(), "qsel_pick_kernel launch");
+  }
+  hipLaunchKernelGGL(sdo::qsel_final_kernel, dim3((unsigned)((G * nfrac + 255) / 256)), dim3(256), 0, s, st, nfrac,
+                     is_f64, div, (uint64_t*)out);
+  check(hipGetLastError(), "qsel_final_kernel launch");
+}
+
+// ---------------------------------------------------------------------------------------------
 // Peer-to-peer mailboxes (p2p.hip): one allocation per (process group, rank), exported with an IPC
 // handle and opened by every peer; the small dense merge is then one kernel per rank.
 // The mailbox is UNCACHED device memory: the writer's stores and the peers' xGMI reads meet in
@@ -1114,6 +1198,8 @@ PYBIND11_MODULE(_sdo_native, m) {
   m.def("part_tune", &part_tune, py::arg("pu"), py::arg("lds_min") = 0);
   m.def("part_hash_agg_hll", &part_hash_agg_hll);
   m.def("theta_select_regions", &theta_select_regions);
+  m.def("qsel_stats", &qsel_stats);
+  m.def("qsel_select", &qsel_select);
   m.def("part_agg", &part_agg);
   m.def("part_agg_topk", &part_agg_topk);
   m.def("part_agg_hll", [](uint64_t recs, int RW, uint64_t base, int64_t nsub, int64_t G, int shift, std::vector<int> slot,

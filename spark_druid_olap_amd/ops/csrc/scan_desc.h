@@ -101,7 +101,9 @@ enum AKind : int32_t {
   A_SUM_X = 8,  // exact decimal expression sum: llrint(expr) (expr pre-scaled by 10^scale) into S_SUM_I
   A_HLL_STORED = 9,  // union of the row's stored (rolled-up) HLL sketch into the group's registers (JIT only)
   A_ROWID = 10,      // emit producers: the row id as a record field (JIT only)
-  A_HLL_CODE = 11    // HLL over a code column: u16 (bucket << 5 | rho) per row (segment/hllcode.py)
+  A_HLL_CODE = 11,   // HLL over a code column: u16 (bucket << 5 | rho) per row (segment/hllcode.py)
+  A_THETA = 12,      // theta producers: the 62-bit KMV hash of the column's value (JIT only)
+  A_QVAL = 13        // quantile producers: the column's value as an order-preserving u64 (JIT only)
 };
 // accumulator slot update ops
 enum SlotOp : int32_t { S_SUM_I = 0, S_SUM_F = 1, S_MIN_I = 2, S_MAX_I = 3 };

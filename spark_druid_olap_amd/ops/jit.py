@@ -125,6 +125,9 @@ def part_fields(prog, cols=None) -> List[Tuple[int, int]]:
         if kind == D.A_THETA:
             out.append((a["slot"], 2))  # 62-bit KMV hash (theta producers, engine/device_exec.py PreparedTheta)
             continue
+        if kind == D.A_QVAL:
+            out.append((a["slot"], 2))  # ordered u64 value (quantile producers, engine/device_exec.py PreparedQuantile)
+            continue
         w = 2
         if kind in (D.A_SUM_I, D.A_MIN_I, D.A_MAX_I) and not a.get("expr") and a.get("col") in cols:
             c = cols[a["col"]]
@@ -768,6 +771,12 @@ class _Gen:
                     # the thetaSketch hash of the row's value: theta_hash (segment/ingest.py) in-kernel
                     val = (f"(int64_t)(mix64((uint64_t)(int64_t)({self.ival(a['col'])}) ^ 0x5BD1E995ull) & "
                            "0x3FFFFFFFFFFFFFFFull)")
+                elif kind == D.A_QVAL:
+                    # the value as an order-preserving u64 (ops/csrc/quantile.hip): integers with the
+                    # sign bit flipped, doubles through f2ord's signed order first
+                    c = self.cols[a["col"]]
+                    sv = f"f2ord({self.dval(a['col'])})" if c.flt else f"(int64_t)({self.ival(a['col'])})"
+                    val = f"(int64_t)((uint64_t)({sv}) ^ 0x8000000000000000ull)"
                 elif kind == D.A_COUNT:
                     val = "1LL"
                 elif kind == D.A_SUM_X:

@@ -470,7 +470,7 @@ def plan_key_passes(prep) -> int:
     if prog.est_rows < prog.G / 4:
         return 1  # few groups touched (first-touch table, TPC-H Q3): the atomics are sparse anyway
     table = prog.G * max(1, prog.nslots) * 8
-    if table <= 2 * MALL_BYTES or prog.nhll or prog.thetas or getattr(prog, "stored_hll", None):
+    if table <= 2 * MALL_BYTES or prog.nhll or prog.needs_rows or getattr(prog, "stored_hll", None):
         return 1
     return int(math.ceil(table / PASS_TABLE_BYTES))
 

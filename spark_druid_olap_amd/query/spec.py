@@ -500,6 +500,20 @@ class ThetaSketchAggregationSpec(Spec, _Decodable):
     type: str = "thetaSketch"
 
 
+@_register("aggregation", "quantiles")
+@dataclass
+class QuantilesAggregationSpec(Spec, _Decodable):
+    """Exact per-group order statistics of a numeric column: one value per fraction in the result
+    column.  ``interpolate``: Spark's ``percentile`` (linear interpolation between the ranks
+    floor / ceil of p (n-1), a double); otherwise the element at rank max(0, ceil(p n) - 1)
+    (``percentile_approx``'s contract, met exactly), of the column's own type."""
+    name: str
+    fieldName: str
+    fractions: List[float] = field(default_factory=list)
+    interpolate: bool = True
+    type: str = "quantiles"
+
+
 # ============================================================================ post aggregations
 @_register("postagg", "fieldAccess")
 @dataclass

@@ -212,8 +212,8 @@ class StreamedQuery:
         # lower once over the whole host shard (CPU): which columns every window must carry
         host_pq = PreparedQuery(_HostEngine(engine), qs, shard.ds)
         self._cols = _columns_of(host_pq._full_prog)
-        if host_pq._full_prog.thetas:
-            raise LoweringError("thetaSketch aggregations are not streamed")
+        if host_pq._full_prog.needs_rows:
+            raise LoweringError("thetaSketch / quantiles aggregations are not streamed")
         self.stats: Dict[str, float] = {}
 
     def run(self):

@@ -142,7 +142,10 @@ class Alias(Expr):
 
 AGG_FUNCS = {"count", "sum", "min", "max", "avg", "mean", "approx_count_distinct", "first", "last",
              "stddev", "stddev_samp", "stddev_pop", "variance", "var_samp", "var_pop", "collect_set",
-             "collect_list", "grouping", "grouping_id"}
+             "collect_list", "grouping", "grouping_id", "percentile", "median", "percentile_approx",
+             "approx_percentile"}
+# exact order statistics (query/spec.py QuantilesAggregationSpec)
+QUANTILE_FUNCS = {"percentile", "median", "percentile_approx", "approx_percentile"}
 
 
 @dataclass(frozen=True, repr=False)

@@ -33,9 +33,9 @@ from ..query import transforms as QT
 from ..query.intervals import fmt_iso
 from . import ast as A
 from . import plan as P
-from .functions import Frame, Period, constant_fold, evaluate, is_deterministic, typeof
+from .functions import Frame, Period, constant_fold, evaluate, is_deterministic, quantile_args, typeof
 from .jscodegen import JSGenError, js_aggregator, js_expr, js_single_column_fn, vm_compatible
-from .types import AnalysisError, base, is_vec, to_series
+from .types import AnalysisError, INTEGRAL, base, is_vec, to_series
 
 DAY_MS = 86_400_000
 MIN_MS = -(2 ** 62)
@@ -657,6 +657,7 @@ class DruidRewriter:
             columns.append((spec.outputName, t, kind))
             final[outs[i].rid] = r
         aggs = []
+        shared = {}
         for j, a in enumerate(agg.aggs):
             call = a.child
             call = A.Call(call.name, tuple(pf.sub(x) for x in call.args), call.distinct)
@@ -666,8 +667,13 @@ class DruidRewriter:
             prefs = []
             for part in parts:
                 spec_, t = part[0], part[1]
+                if id(spec_) in shared:  # (a quantiles aggregator several calls read)
+                    prefs.append(shared[id(spec_)])
+                    continue
                 aggs.append(spec_)
                 r = A.Ref(A.new_id(), spec_.name, t)
+                if isinstance(spec_, S.QuantilesAggregationSpec):
+                    shared[id(spec_)] = r
                 drefs.append(r)
                 columns.append((spec_.name, t, part[2] if len(part) > 2 else "value"))
                 prefs.append(r)
@@ -878,7 +884,60 @@ class DruidRewriter:
                 return [(spec_, t), (cnt, ct)], \
                     lambda rs: A.BinOp("/", A.Cast(rs[0], "double"), rs[1])
             return [(spec_, t)], lambda rs: rs[0]
+        if n in A.QUANTILE_FUNCS:
+            return self._quantile_agg(pf, call, names, rolled)
         raise NotPushable(f"aggregate {n} is not pushable")
+
+    def _quantile_agg(self, pf: PF, call: A.Call, names: "_Names", rolled: bool):
+        """percentile / median / percentile_approx over a plain metric (long, decimal, double) or a
+        dimension with a LONG / DOUBLE dictionary -> ONE ``quantiles`` aggregator per (column,
+        interpolate) pair of the query; each call projects its fractions out of the aggregator's
+        result column (one array per group).  The select is exact on one rank only: a distributed
+        session answers on the host."""
+        from ..segment.dictionary import DOUBLE, LONG
+
+        n = call.name
+        fr, interp, is_arr = quantile_args(call)
+        if rolled:
+            raise NotPushable(f"{n} over a rolled-up datasource")
+        if self.session.engine.world.distributed:
+            raise NotPushable("percentile across ranks")
+        x = call.args[0]
+        if not isinstance(x, A.Ref):
+            raise NotPushable(f"{n} over an expression")
+        c = self._column(pf, x)
+        ds = pf.table.info.datasource
+        if c.is_metric:
+            m = ds.metrics.get(c.druid_column)
+            if m is None or m.sketch is not None or m.kind not in ("long", "decimal", "double"):
+                raise NotPushable(f"{n} over the sketch metric {c.column}")
+        elif c.kind == "dimension" and not c.is_time:
+            dc = ds.dims.get(c.druid_column)
+            if dc is None or dc.dictionary.vtype not in (LONG, DOUBLE):
+                raise NotPushable(f"{n} over the non-numeric dimension {c.column}")
+        else:
+            raise NotPushable(f"{n} over {c.column}")
+        spec = names.quantiles.get((c.druid_column, interp))
+        if spec is None:
+            spec = names.quantiles[(c.druid_column, interp)] = \
+                S.QuantilesAggregationSpec(names.agg(), c.druid_column, [], interp)
+        at = []
+        for p in fr:
+            if p not in spec.fractions:
+                spec.fractions.append(p)
+            at.append(spec.fractions.index(p))
+        xt = typeof(x)
+        fn = "__quantile_at" if interp or base(xt) not in INTEGRAL else "__quantile_at_long"
+
+        def element(r, i):
+            e = A.Call(fn, (r, A.Lit(i, "int")))
+            # (percentile_approx answers an element of the column: the column's own type, as the host plan)
+            return e if interp or typeof(e) == xt else A.Cast(e, xt)
+
+        def project(rs):
+            el = [element(rs[0], i) for i in at]
+            return A.Call("array", tuple(el)) if is_arr else el[0]
+        return [(spec, "array")], project
 
     def _filtered_agg(self, pf: PF, n: str, x: A.Expr, names: "_Names", count_spec):
         """``sum(CASE WHEN p THEN v ELSE 0 END)`` -> Druid filtered aggregator (filter p over sum(v),
@@ -1352,6 +1411,7 @@ class _Names:
     def __init__(self):
         self.n = 0
         self.used: Set[str] = set()
+        self.quantiles: Dict[tuple, object] = {}  # (column, interpolate) -> its one quantiles aggregator
 
     def agg(self) -> str:
         self.n += 1

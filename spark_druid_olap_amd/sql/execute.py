@@ -18,8 +18,8 @@ import pandas as pd
 from ..query import spec as S
 from . import ast as A
 from . import plan as P
-from .functions import Frame, eval_series, evaluate, typeof
-from .types import AnalysisError, base, broadcast, fast_series, is_vec, pandas_dtype, to_series
+from .functions import Frame, eval_series, evaluate, quantile_args, typeof
+from .types import AnalysisError, INTEGRAL, base, broadcast, fast_series, is_vec, pandas_dtype, to_series
 
 
 def take_series(v: pd.Series, idx: np.ndarray) -> pd.Series:
@@ -797,6 +797,8 @@ def druid_value_lazy(col, sqlt: str, kind: str, n: int):
         _DictColumn = _DC
     if type(col) is _DictColumn:
         return LazySeries(None, None, (col, sqlt))
+    if getattr(col, "ndim", 1) == 2:  # a quantiles aggregator: one array of values per group
+        return pd.Series(list(col), dtype=object)
     if kind != "time":
         if type(col) is np.ndarray:
             # (the common numeric result columns: already at their final numpy dtype)
@@ -1017,6 +1019,8 @@ def _agg_one(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, n: int, out_t:
     if name == "count" and not call.args:
         cnt = np.bincount(codes, minlength=ng) if n else np.zeros(ng, dtype=np.int64)
         return pd.Series(cnt.astype(np.int64), dtype="Int64")
+    if name in A.QUANTILE_FUNCS:
+        return _agg_quantile(call, fr, codes, ng, out_t)
     args = [eval_series(a, fr) for a in call.args]
     x = args[0] if args else None
     if name == "count":
@@ -1084,6 +1088,43 @@ def _agg_one(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, n: int, out_t:
         r = g.agg(lambda v: list(v) if name == "collect_list" else sorted(set(v), key=str)).reindex(range(ng))
         return pd.Series(r.to_numpy(), dtype=object)
     raise AnalysisError(f"unsupported aggregate {name}")
+
+
+def _agg_quantile(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, out_t: str) -> pd.Series:
+    """percentile / median (Spark's exact semantics: linear interpolation at p (n-1)) and
+    percentile_approx (the element at rank max(0, ceil(p n) - 1)) per group, NULLs ignored."""
+    fracs, interp, is_arr = quantile_args(call)
+    x = eval_series(call.args[0], fr)
+    valid = ~x.isna().to_numpy()
+    xv = x[valid]
+    integral = base(typeof(call.args[0])) in INTEGRAL
+    xv = xv.to_numpy(dtype=np.int64) if integral else xv.astype("float64").to_numpy(dtype=np.float64)
+    c = codes[valid]
+    order = np.lexsort((xv, c))
+    vs = xv[order]
+    cnt = np.bincount(c, minlength=ng).astype(np.int64) if len(c) else np.zeros(ng, dtype=np.int64)
+    start = np.cumsum(cnt) - cnt
+    have = cnt > 0
+    n, s0 = cnt[have].astype(np.float64), start[have]
+    p = np.asarray(fracs, dtype=np.float64)
+    if interp:
+        pos = p[None, :] * (n[:, None] - 1.0)
+        lo_r = np.floor(pos)
+        lo = vs[s0[:, None] + lo_r.astype(np.int64)].astype(np.float64)
+        hi = vs[s0[:, None] + np.ceil(pos).astype(np.int64)].astype(np.float64)
+        gm = pos - lo_r  # (anchored at the nearer rank: no cancellation error across a sign change)
+        res = np.where(gm >= 0.5, hi - (hi - lo) * (1.0 - gm), lo + (hi - lo) * gm)
+    else:
+        res = vs[s0[:, None] + np.maximum(np.ceil(p[None, :] * n[:, None]) - 1.0, 0.0).astype(np.int64)]
+    full = np.empty(ng, dtype=object)
+    full[:] = None
+    idx = np.flatnonzero(have)
+    if is_arr:
+        for i, r in zip(idx, res):
+            full[i] = r.tolist()
+        return pd.Series(full, dtype=object)
+    full[idx] = res[:, 0].tolist() if len(idx) else []
+    return to_series(pd.Series(full, dtype=object), out_t)
 
 
 def aggregate(p: P.Aggregate, b: Batch, subq=None) -> Batch:

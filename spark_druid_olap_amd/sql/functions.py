@@ -64,6 +64,43 @@ def _widest(ts):
 
 # ------------------------------------------------------------------------------------------------
 # typing
+def quantile_args(call: A.Call):
+    """(fractions, interpolate, array form) of a percentile / median / percentile_approx call.  The
+    percentage is a literal in [0, 1], or -- ``percentile`` only -- ``array(...)`` of such literals;
+    percentile_approx's accuracy argument is accepted and ignored."""
+    n = call.name
+    interp = n in ("percentile", "median")
+    want = (1, 1) if n == "median" else ((2, 2) if n == "percentile" else (2, 3))
+    if not (want[0] <= len(call.args) <= want[1]):
+        raise AnalysisError(f"{n} takes {want[0]}" + (f"..{want[1]}" if want[1] != want[0] else "") + " arguments")
+    if call.distinct:
+        raise AnalysisError(f"{n}(DISTINCT) is not supported")
+    if n == "median":
+        return [0.5], True, False
+    p = call.args[1]
+    is_arr = isinstance(p, A.Call) and p.name == "array"
+    if is_arr and not interp:
+        raise AnalysisError(f"{n}: an array of percentages is supported by percentile only")
+    lits = list(p.args) if is_arr else [p]
+    out = []
+    for x in lits:
+        v = x.value if isinstance(x, A.Lit) else None
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0.0 <= float(v) <= 1.0):
+            raise AnalysisError(f"{n}: the percentage must be a literal between 0.0 and 1.0, got {x.sql()}")
+        out.append(float(v))
+    if not out:
+        raise AnalysisError(f"{n}: empty percentage array")
+    return out, interp, is_arr
+
+
+def quantile_type(call: A.Call) -> str:
+    _, interp, is_arr = quantile_args(call)
+    t = typeof(call.args[0])
+    if base(t) not in INTEGRAL and base(t) not in ("double", "float", "decimal"):
+        raise AnalysisError(f"{call.name} over the non-numeric type {t}")
+    return "array" if is_arr else ("double" if interp else t)
+
+
 def agg_type(name: str, ts: Sequence[str]) -> str:
     if name == "count" or name == "approx_count_distinct":
         return "bigint"
@@ -128,6 +165,8 @@ def typeof(e: A.Expr) -> str:
             return typeof(f.args[0]) if f.args else "null"
         return typeof(f)
     if isinstance(e, A.Call):
+        if e.name in A.QUANTILE_FUNCS:
+            return quantile_type(e)
         ts = [typeof(a) for a in e.args]
         if e.is_agg:
             return agg_type(e.name, ts)
@@ -1288,6 +1327,26 @@ def _misc_ids(args, ts, n):
 @_reg("element_at", _const("string"))
 def _element_at(args, ts, n):
     return _map_scalar(lambda a, i: a[int(i) - 1] if 0 < int(i) <= len(a) else None, "string")(args, ts, n)
+
+
+@_reg("array", _const("array"))
+def _array(args, ts, n):
+    cols = [a.tolist() if is_vec(a) else [a] * n for a in args]
+    return pd.Series([list(r) for r in zip(*cols)] if cols else [[] for _ in range(n)], dtype=object)
+
+
+def _quantile_at(args, ts, n):
+    # element i of a pushed quantiles aggregator's result column (one array per group)
+    v, i = args[0], int(args[1])
+    rows = v.tolist() if is_vec(v) else [v] * n
+    vals = [r[i] if isinstance(r, (list, tuple, np.ndarray)) else None for r in rows]
+    if any(x is None for x in vals):
+        return pd.Series([x.item() if isinstance(x, np.generic) else x for x in vals], dtype=object)
+    return pd.Series(np.asarray(vals))
+
+
+_reg("__quantile_at", _const("double"))(_quantile_at)
+_reg("__quantile_at_long", _const("bigint"))(_quantile_at)
 
 
 @_reg("size", _const("int"))

@@ -250,6 +250,8 @@ def to_series(values, t: str) -> pd.Series:
         s = values.reset_index(drop=True)
     else:
         s = pd.Series(values)
+    if t == "array" and s.dtype == object:
+        return s  # (one Python list per row: percentile(x, array(...)), collect_list)
     if pdt == "datetime64[ns]":
         if s.dtype.kind == "M":
             out = s.astype("datetime64[ns]")
