@@ -1440,14 +1440,17 @@ def arena_bytes() -> int:
 
 def device_memory_report() -> dict:
     """Where the device memory is (GB): the allocator's totals, the slot arenas, the partition
-    scratch, the slot-0 cached scan buffers, and the release / retry events so far."""
+    scratch, the slot-0 cached scan buffers, the dictionaries' text heaps, and the release / retry
+    events so far."""
+    from ..utils.memory import dict_cache_bytes
     from ..utils.metrics import events
 
     g = 1e9
     out = {"arenas_gb": round(arena_bytes() / g, 3),
            "arena_per_slot_gb": {f"{k[1]}": round(a.cap / g, 3) for k, a in sorted(_ARENAS.items(), key=lambda x: x[0][1])},
            "part_scratch_gb": round(PART_POOL.bytes() / g, 3),
-           "slot0_bufs_gb": round(_buf_total[0] / g, 3), "events": events()}
+           "slot0_bufs_gb": round(_buf_total[0] / g, 3), "dict_text_heaps_gb": round(dict_cache_bytes() / g, 3),
+           "events": events()}
     if torch.cuda.is_available():
         ms = torch.cuda.memory_stats()
         out.update(allocated_gb=round(torch.cuda.memory_allocated() / g, 2),

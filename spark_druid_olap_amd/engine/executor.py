@@ -198,7 +198,8 @@ class PreparedQuery:
         self.world = engine.world
         ctx = getattr(qs, "context", None)
         self.deterministic = bool(engine.deterministic or (ctx is not None and getattr(ctx, "deterministic", None)))
-        self.low = Lowerer(ds, world=engine.world, deterministic=self.deterministic)
+        self.low = Lowerer(ds, world=engine.world, deterministic=self.deterministic,
+                           device_match=is_cuda_ds(ds) and bool(engine.use_native))
         self.scans: List[tuple] = []  # (tag, prog, prepared)
         self.segments_per_query = segments_per_query
         self._nbatches: Optional[int] = None   # batch count agreed across ranks (pipelined merge)
@@ -452,6 +453,12 @@ class PreparedQuery:
         """Execute once.  A peer-to-peer merge epoch abandoned by every rank (parallel/p2p.py)
         raises ``P2PRetry`` on every rank together: the statement then re-runs with its merges over
         RCCL, so a slow or unreachable peer costs a retry, not a failed statement."""
+        res = self._run_once()
+        if self.low.dict_match_device:  # id masks the device matcher answered while lowering
+            res.stats["dict_match_device"] = self.low.dict_match_device
+        return res
+
+    def _run_once(self) -> QueryResult:
         fast = self.__dict__.get("_fast")
         if fast is None:
             fast = self._fast = _SmallDenseRunner.build(self) or False
@@ -1630,7 +1637,9 @@ def _search_filter(dim: str, q):
     t = q.type
     if t == "fragment":
         vals = [v.lower() for v in (q.values or [])]
-        return _PyFilter(dim, lambda v: v is not None and all(x in str(v).lower() for x in vals))
+        f = _PyFilter(dim, lambda v: v is not None and all(x in str(v).lower() for x in vals))
+        f._pyneedles = vals  # type: ignore[attr-defined]  (the lowerer may hand them to the device matcher)
+        return f
     if t == "regex":
         return S.RegexFilterSpec(dim, str(q.value))
     cs = q.caseSensitive and t != "insensitive_contains"

@@ -30,6 +30,7 @@ from ..query.jsfunc import JSError, compile_function, jsagg_to_expr, parse_expr
 from ..segment.datasource import CHUNK_ROWS, DataSource, dtype_code
 from ..segment.dictionary import Dictionary
 from .columns import DictColumn
+from .dict_match import compile_like, compile_needles
 
 FD_KEYS = True    # (tests / tools: False keeps functionally dependent keys in the scan)
 FOLD_PRESENCE = True  # (tests: False keeps the separate presence-count slot)
@@ -450,8 +451,13 @@ def column_tensor(ds: DataSource, name: str) -> torch.Tensor:
 class Lowerer:
     """QuerySpec -> ScanProgram for a datasource shard."""
 
-    def __init__(self, ds: DataSource, bitmap_max_values: int = 4, world=None, deterministic: bool = False):
+    def __init__(self, ds: DataSource, bitmap_max_values: int = 4, world=None, deterministic: bool = False,
+                 device_match: bool = False):
         self.ds = ds
+        # LIKE / contains / fragment leaves over large materialized string dictionaries are matched
+        # by the device kernel (engine/dict_match.py); the executor sets it for native GPU runs
+        self.device_match = device_match
+        self.dict_match_device = 0  # id masks the device matched (the prepared query's stats)
         self.bitmap_max_values = bitmap_max_values
         self.world = world
         # floating-point sums in exact 64.32 fixed point (two integer slots) instead of f64 atomics:
@@ -464,6 +470,18 @@ class Lowerer:
     def filter_ir(self, f) -> tuple:
         """Filter spec -> normalized boolean IR (constant-folded id-set leaves)."""
         return b_and([self._filter_ir(f)])
+
+    def _device_mask(self, d: Dictionary, program, recheck=None) -> Optional[np.ndarray]:
+        """The id mask of a compiled text predicate from the device matcher, or None: not a native
+        GPU run, a dictionary below the crossover, or one of the matcher's own refusals."""
+        from . import dict_match
+
+        if not self.device_match or len(d) < dict_match.DEVICE_MIN_CARD:
+            return None
+        m = dict_match.match_mask(d, self.ds.device, program() if callable(program) else program, recheck)
+        if m is not None:
+            self.dict_match_device += 1
+        return m
 
     def _filter_ir(self, f) -> tuple:
         ds = self.ds
@@ -533,10 +551,11 @@ class Lowerer:
             q = f.query or {}
             val = str(q.get("value", ""))
             cs = bool(q.get("caseSensitive", False)) and q.get("type") != "insensitive_contains"
-            if cs:
-                return ("ids", dim, d.eval_mask(lambda v: v is not None and val in str(v)))
-            lv = val.lower()
-            return ("ids", dim, d.eval_mask(lambda v: v is not None and lv in str(v).lower()))
+            lv = val if cs else val.lower()
+            pred = (lambda v: v is not None and val in str(v)) if cs else \
+                (lambda v: v is not None and lv in str(v).lower())
+            m = self._device_mask(d, lambda: compile_needles([lv], not cs), pred)
+            return ("ids", dim, m if m is not None else d.eval_mask(pred))
         if isinstance(f, S.ExtractionFilterSpec):
             ef = f.extractionFn
             if isinstance(ef, S.InExtractionFnSpec) and _druid_str(f.value) == "true" and \
@@ -569,6 +588,19 @@ class Lowerer:
                         m = ~m
                         if d.has_null:
                             m[0] = False
+                    return ("ids", dim, m)
+            if pl is not None:  # bare [NOT] LIKE over a materialized dictionary: the device matcher
+                m = self._device_mask(d, lambda: compile_like(pl[0]))
+                if m is not None:
+                    if pl[1]:
+                        m = ~m
+                        if d.has_null:
+                            m[0] = False
+                    return ("ids", dim, m)
+            nd = getattr(f, "_pyneedles", None)
+            if nd is not None:  # search 'fragment': every (lowered) needle present, case-folded
+                m = self._device_mask(d, lambda: compile_needles(nd, True), f._pyfn)
+                if m is not None:
                     return ("ids", dim, m)
             pv = getattr(f, "_pyvec", None)
             if pv is not None:  # vectorised dictionary-domain predicate (SQL planner)

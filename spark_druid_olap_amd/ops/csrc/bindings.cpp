@@ -22,6 +22,7 @@
 #include "scan_desc.h"
 #include "post_scan.h"
 #include "quantile.h"
+#include "dict_match.h"
 
 namespace sdo {
 template <int U>
@@ -101,6 +102,10 @@ __global__ void qsel_hist_regions_kernel(const uint32_t* recs, int rw, int voff,
                                          const uint32_t* seg_hi, int64_t nseg, QselState s, int level, int use_lds);
 __global__ void qsel_pick_kernel(QselState s, int level);
 __global__ void qsel_final_kernel(QselState s, int nfrac, int is_f64, double div, uint64_t* out);
+// dict_match.hip (DmProgram: dict_match.h)
+template <bool FOLD>
+__global__ void dict_match_kernel(const uint8_t* __restrict__ heap, const uint32_t* __restrict__ off, uint32_t n,
+                                  DmProgram prog, uint64_t* __restrict__ out, uint64_t* __restrict__ nonascii);
 // p2p.hip (P2PArgs: p2p.h)
 __global__ void p2p_merge_kernel(P2PArgs a);
 }  // namespace sdo
@@ -949,6 +954,54 @@ static void qsel_select(uint64_t recs, int rw, int voff, uint64_t seg_lo, uint64
 }
 
 // ---------------------------------------------------------------------------------------------
+// LIKE / contains / fragment over a dictionary's device text heap (dict_match.hip): bit e of `out`
+// says entry e matches `program` (a packed DmProgram); when the program folds case, bit e of
+// `nonascii` says entry e holds a byte >= 0x80 (the host re-evaluates those).  `heap` is 16-byte
+// aligned and `heap_bytes` -- what may be read -- a multiple of 16 covering off[n]; `off` holds
+// n + 1 ascending u32 byte offsets; both outputs hold ceil(n / 64) words.
+static void dict_match(uint64_t heap, uint64_t heap_bytes, uint64_t off, int64_t n, uint64_t text_bytes,
+                       py::bytes program, uint64_t out, uint64_t nonascii, uint64_t stream) {
+  const std::string ps(program);
+  if (ps.size() != sizeof(sdo::DmProgram)) throw std::invalid_argument("dict_match: program size");
+  sdo::DmProgram prog;
+  std::memcpy(&prog, ps.data(), sizeof(prog));
+  if (prog.nseg < 0 || prog.nseg > sdo::DM_MAX_SEGS) throw std::invalid_argument("dict_match: 0..8 segments");
+  for (int s = 0; s < prog.nseg; ++s)
+    if (prog.len[s] > sdo::DM_MAX_SEG_LEN) throw std::invalid_argument("dict_match: segment longer than 256");
+  const int anchors = sdo::DM_ANCHOR_START | sdo::DM_ANCHOR_END;
+  if ((prog.flags & anchors) && (prog.nseg < 1 || (prog.flags & sdo::DM_ALL)))
+    throw std::invalid_argument("dict_match: anchors need a segment and exclude AND-of-needles");
+  if (n <= 0) return;
+  if (n > (int64_t)0xffffff00u) throw std::invalid_argument("dict_match: too many entries");
+  if (!heap || (heap & 15) || (heap_bytes & 15) || heap_bytes > ((uint64_t)1 << 32) || text_bytes > heap_bytes)
+    throw std::invalid_argument("dict_match: heap must be 16-byte aligned and padded, below 4 GiB");
+  if (!off || (off & 3) || !out || (out & 7)) throw std::invalid_argument("dict_match: offsets / output");
+  const bool fold = (prog.flags & sdo::DM_FOLD) != 0;
+  if (fold && (!nonascii || (nonascii & 7))) throw std::invalid_argument("dict_match: folding needs the non-ASCII bitset");
+  const dim3 grid((unsigned)((n + sdo::DM_BLOCK - 1) / sdo::DM_BLOCK)), block(sdo::DM_BLOCK);
+  hipStream_t s = (hipStream_t)stream;
+  if (fold)
+    hipLaunchKernelGGL(sdo::dict_match_kernel<true>, grid, block, 0, s, (const uint8_t*)heap, (const uint32_t*)off,
+                       (uint32_t)n, prog, (uint64_t*)out, (uint64_t*)nonascii);
+  else
+    hipLaunchKernelGGL(sdo::dict_match_kernel<false>, grid, block, 0, s, (const uint8_t*)heap, (const uint32_t*)off,
+                       (uint32_t)n, prog, (uint64_t*)out, (uint64_t*)nullptr);
+  check(hipGetLastError(), "dict_match_kernel launch");
+}
+
+static py::dict dict_match_layout() {
+  py::dict d;
+  d["DmProgram"] = sizeof(sdo::DmProgram);
+  d["max_segs"] = sdo::DM_MAX_SEGS;
+  d["max_seg_len"] = sdo::DM_MAX_SEG_LEN;
+  d["tile_bytes"] = sdo::DM_TILE_BYTES;
+  d["off_len"] = offsetof(sdo::DmProgram, len);
+  d["off_lit"] = offsetof(sdo::DmProgram, lit);
+  d["off_any"] = offsetof(sdo::DmProgram, any);
+  return d;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Peer-to-peer mailboxes (p2p.hip): one allocation per (process group, rank), exported with an IPC
 // handle and opened by every peer; the small dense merge is then one kernel per rank.
 // The mailbox is UNCACHED device memory: the writer's stores and the peers' xGMI reads meet in
@@ -1200,6 +1253,8 @@ PYBIND11_MODULE(_sdo_native, m) {
   m.def("theta_select_regions", &theta_select_regions);
   m.def("qsel_stats", &qsel_stats);
   m.def("qsel_select", &qsel_select);
+  m.def("dict_match", &dict_match);
+  m.def("dict_match_layout", &dict_match_layout);
   m.def("part_agg", &part_agg);
   m.def("part_agg_topk", &part_agg_topk);
   m.def("part_agg_hll", [](uint64_t recs, int RW, uint64_t base, int64_t nsub, int64_t G, int shift, std::vector<int> slot,

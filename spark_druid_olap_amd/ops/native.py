@@ -336,6 +336,22 @@ def hll_merge_stored(regs: torch.Tensor, rows: torch.Tensor, gid: torch.Tensor, 
                        offsets.data_ptr(), pairs.data_ptr(), int(p), int(G), regs.data_ptr(), _stream(regs.device))
 
 
+def dict_match(heap: torch.Tensor, offsets: torch.Tensor, n: int, text_bytes: int, program: bytes,
+               words: torch.Tensor, nonascii_at: int) -> None:
+    """Bit e of ``words`` = entry e of a dictionary text heap (segment/textheap.py) matches the packed
+    pattern ``program`` (dict_match.hip; engine/dict_match.py compiles it).  ``nonascii_at`` > 0: the
+    program folds case and the non-ASCII bitset goes to ``words[nonascii_at:]``."""
+    m = load()
+    nw = (n + 63) // 64
+    assert heap.dtype == torch.uint8 and heap.is_cuda and heap.is_contiguous() and heap.numel() % 16 == 0
+    assert offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() == n + 1
+    assert words.dtype == torch.int64 and words.is_contiguous() and words.device == heap.device
+    assert nonascii_at in (0, nw) and words.numel() >= nw + (nw if nonascii_at else 0)
+    assert 0 <= text_bytes <= heap.numel()
+    m.dict_match(heap.data_ptr(), heap.numel(), offsets.data_ptr(), int(n), int(text_bytes), program,
+                 words.data_ptr(), words.data_ptr() + 8 * nonascii_at if nonascii_at else 0, _stream(heap.device))
+
+
 def run_scan(acc, init, rows, nslots, zptr, zwords, overflow, jit, desc, grid, block, lds, unroll, stream) -> None:
     """Fused buffer reset + scan kernel of a prepared scan (arguments cached by the caller)."""
     load().run_scan(acc, init, rows, nslots, zptr, zwords, overflow, jit, desc, grid, block, lds, unroll, stream)

@@ -82,3 +82,20 @@ def reserve_runtime_memory(device=None) -> float:
     frac = max(0.5, 1.0 - RUNTIME_RESERVE / total)
     torch.cuda.set_per_process_memory_fraction(frac, dev)
     return frac
+
+
+# Device bytes held by dictionary-level caches that live on the dictionary objects themselves (the
+# text heaps of segment/textheap.py), per device: engine/device_exec.py device_memory_report shows
+# them beside the arenas and scan buffers, and a new heap is priced against what is already held.
+_DICT_CACHE_BYTES: dict = {}
+
+
+def note_dict_cache_bytes(dev, delta: int) -> None:
+    k = str(dev)
+    _DICT_CACHE_BYTES[k] = max(0, _DICT_CACHE_BYTES.get(k, 0) + int(delta))
+
+
+def dict_cache_bytes(dev=None) -> int:
+    if dev is None:
+        return sum(_DICT_CACHE_BYTES.values())
+    return _DICT_CACHE_BYTES.get(str(dev), 0)
