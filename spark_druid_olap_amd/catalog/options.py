@@ -135,6 +135,10 @@ CONF_ENTRIES: List[ConfEntry] = [
     # MI355X engine knobs (new)
     ConfEntry("spark.sparklinedata.druid.approxCountDistinct", False,
               "push COUNT(DISTINCT x) as a cardinality (HLL) aggregator instead of the exact 2-level rewrite", bool),
+    ConfEntry("spark.sparklinedata.druid.distinctCount.pushdown", "same-shape",
+              "exact COUNT(DISTINCT dim) as a distinctCount aggregator (native GPU engine, one rank): off | same-shape "
+              "(statements without other aggregates: as many Druid queries as the two-level plan) | all (also next to "
+              "sum / count / ...: one query instead of two and a join)"),
     ConfEntry("spark.sparklinedata.druid.planCache.enabled", True, "cache optimized plans by SQL text", bool),
     ConfEntry("spark.sparklinedata.druid.query.timeout.ms", 0, "per-query deadline (0 = none)", int),
     ConfEntry("spark.sparklinedata.druid.fuse.groupingsets", True,

@@ -24,7 +24,7 @@ import torch
 
 from ..ops import desc as D
 from ..ops import native
-from .lower import ScanProgram, pack
+from .lower import ScanProgram, distinct_null_id, pack
 from .partials import Partials
 from .scheduler import current_slot
 
@@ -1485,7 +1485,7 @@ class PreparedEmit:
         ep = copy.copy(prog)
         ep.aops = [{"kind": D.A_ROWID, "col": -1, "expr": None, "filter": None, "slot": 0, "hll": -1}]
         ep.slots = [(D.S_SUM_I, 0)]
-        ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.packed = 0, [], [], [], {}
+        ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.packed = 0, [], [], [], [], {}
         ep.presence_only = False
         self.prog = ep
         self.dev = prog.ds.device
@@ -1556,7 +1556,7 @@ def theta_producer_prog(prog: ScanProgram, cols: List[str]) -> ScanProgram:
     ep.aops = [{"kind": D.A_THETA, "col": ep.col(c), "expr": None, "filter": None, "slot": i, "hll": -1}
                for i, c in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(cols)
-    ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.packed = 0, [], [], [], {}
+    ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.packed = 0, [], [], [], [], {}
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("theta: program not eligible")
@@ -1742,7 +1742,7 @@ def quantile_producer_prog(prog: ScanProgram, cols: List[str]) -> ScanProgram:
     ep.aops = [{"kind": D.A_QVAL, "col": ep.col(c), "expr": None, "filter": None, "slot": i, "hll": -1}
                for i, c in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(cols)
-    ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.packed = 0, [], [], [], {}
+    ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.packed = 0, [], [], [], [], {}
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("quantile: program not eligible")
@@ -1864,6 +1864,105 @@ class PreparedQuantile:
         finally:
             PART_POOL.release(slab)
         return out
+
+
+def distinct_producer_prog(prog: ScanProgram, cols: list) -> ScanProgram:
+    """The scan program of a distinct producer: ``prog``'s filter, ranges and group key, one
+    A_DISTINCT aggregator (the dimension's dictionary id, one record word) per (column, aggregator
+    filter span) of ``cols``, no other aggregator.  RuntimeError where it does not apply."""
+    import copy
+
+    from ..ops import jit as J
+
+    ep = copy.copy(prog)
+    ep.pcols, ep.fcols, ep.section = list(prog.pcols), list(prog.fcols), "p"
+    ep.aops = [{"kind": D.A_DISTINCT, "col": ep.col(c), "expr": None, "filter": None, "slot": i, "hll": -1,
+                "filt_off": off, "filt_len": n} for i, (c, (off, n)) in enumerate(cols)]
+    ep.slots = [(D.S_SUM_I, 0)] * len(cols)
+    ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.packed = 0, [], [], [], [], {}
+    ep.presence_only = False
+    if not J.part_eligible(ep) or J.part_hashed(ep):
+        raise RuntimeError("distinct: program not eligible")
+    return ep
+
+
+DISTINCT_LDS_WORDS = 64 * 1024 // 4      # u32 words of a workgroup's private bit matrix (ops/csrc/distinct.h)
+DISTINCT_MAX_STATE_BYTES = QSEL_MAX_HIST_BYTES  # cap of the [G][ceil(D / 32)] bit matrix in HBM
+DISTINCT_FORCE_GLOBAL = False            # tests: the global tier for any shape
+
+
+def distinct_tier(G: int, card: int) -> Optional[str]:
+    """Where the [G][ceil(card / 32)] bit matrix of one distinctCount lives: "lds" (a private copy
+    per workgroup), "global" (HBM, test-then-set), or None beyond the cap (the torch fallback)."""
+    words = int(G) * (-(-max(1, int(card)) // 32))
+    if G <= 0 or card >= (1 << 31) or words * 4 > DISTINCT_MAX_STATE_BYTES or words >= (1 << 31):
+        return None
+    return "lds" if words <= DISTINCT_LDS_WORDS and not DISTINCT_FORCE_GLOBAL else "global"
+
+
+class PreparedDistinct:
+    """``distinctCount`` aggregators pushed into the scan: ONE JIT producer pass (ops/jit.py
+    A_DISTINCT) writes (u32 group key, u32 dictionary id per counted column) records of the selected
+    rows into its chunk regions, then per aggregator the bitset and popcount kernels
+    (ops/csrc/distinct.hip) run over them.  Tier and sizes follow from G and the dictionary size, so
+    nothing is read back before the result copy."""
+
+    def __init__(self, prog: ScanProgram, distincts: list):
+        from .lower import lds_layout
+
+        ds = prog.ds
+        if prog.empty or not (0 < prog.G < (1 << 31)):
+            raise RuntimeError("distinct: program not eligible")
+        # aggregators over the same (column, filter) share a record word
+        self.cols = sorted({(c, span) for _, c, _, span in distincts})
+        self.sel = []  # per aggregator: (record word, dictionary size, null id, tier)
+        for _, c, _, span in distincts:
+            dic = ds.dims[c].dictionary
+            tier = distinct_tier(prog.G, len(dic))
+            if tier is None:
+                raise RuntimeError("distinct: bit matrix beyond the cap")
+            self.sel.append((1 + self.cols.index((c, span)), len(dic), distinct_null_id(dic), tier))
+        ep = distinct_producer_prog(prog, self.cols)
+        self.prog, self.dev, self.G = ep, ds.device, int(prog.G)
+        self.jit = _jit_for(ep, D.M_PART, False, 1 << prog.hll_p)
+        if self.jit is None:
+            raise RuntimeError("distinct: no JIT kernel")
+        cache_off, wave_bytes, _, total = lds_layout(ep, 0, UNROLL, BLOCK // 64)
+        d = pack(ep, D.M_PART, 0, 0, 0, 0, 0, 0, 0, 0, 0, [], [], unroll=UNROLL, cache_off=cache_off,
+                 wave_bytes=wave_bytes)
+        self.nch = int(d[0]["total_chunks"])
+        self.grid = _grid(self.dev, self.nch, self.jit.lay.total, self.jit)
+        self.rw = 1 + len(self.cols)
+        cap = self.nch * D.CHUNK_ROWS
+        if cap * self.rw >= (1 << 32):
+            raise RuntimeError("distinct: shard too large for u32 offsets")
+        self.words = max(1, cap * self.rw)
+        self.seg_lo = (torch.arange(self.nch, dtype=torch.int64) * D.CHUNK_ROWS).to(torch.int32).to(self.dev)
+        self._d = d
+        self.tiers = [t for _, _, _, t in self.sel]
+
+    def count(self) -> list:
+        """Per aggregator its counts [G] (host int64)."""
+        nat, st = native.load(), native._stream(self.dev)
+        dev, G = self.dev, self.G
+        pend = torch.empty(max(1, self.nch), dtype=torch.int32, device=dev)
+        slab = PART_POOL.acquire(dev, self.words)
+        try:
+            d = self._d.copy()
+            d[0]["part_recs"] = slab.recs1.data_ptr()
+            d[0]["part_counts"] = pend.data_ptr()
+            desc = _upload(d.view(np.uint8), dev)
+            nat.module_launch(self.jit.handle, desc.data_ptr(), int(self.grid), BLOCK, int(self.jit.lay.total), st)
+            res = []
+            for voff, card, null_id, tier in self.sel:
+                state = torch.empty(G * (-(-card // 32)), dtype=torch.int32, device=dev)
+                out = torch.empty(G, dtype=torch.int64, device=dev)
+                nat.dcount(slab.recs1.data_ptr(), self.rw, voff, self.seg_lo.data_ptr(), pend.data_ptr(), self.nch, G,
+                           card, 0 if tier == "lds" else 1, null_id, state.data_ptr(), out.data_ptr(), st)
+                res.append(out)
+            return [r.cpu().numpy() for r in res]
+        finally:
+            PART_POOL.release(slab)
 
 
 class PreparedMask:

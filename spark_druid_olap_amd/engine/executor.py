@@ -498,7 +498,10 @@ class PreparedQuery:
             with T.span("sdo.post"):
                 self._theta(self._full_prog, cols)
                 self._quantile(self._full_prog, cols)
+                tiers = self._distinct(self._full_prog, cols)
                 res = self._post(prog, cols)
+                if tiers:
+                    res.stats["distinct_count_device"] = tiers
             t4 = time.perf_counter()
             res.stats.update(scan_ms=(t1 - t0) * 1e3, merge_ms=(t2 - t1) * 1e3, finalize_ms=(t3 - t2) * 1e3,
                              post_ms=(t4 - t3) * 1e3)
@@ -1164,6 +1167,62 @@ class PreparedQuery:
             return qp.select()
         except RuntimeError:
             return None
+
+    # ------------------------------------------------------------------ exact distinct counts
+    def _distinct(self, prog: ScanProgram, cols: Dict[str, np.ndarray]) -> Optional[str]:
+        """``distinctCount`` aggregators: per group the number of distinct non-null dictionary ids of
+        the selected rows, an int64 column (0 for groups other aggregators alone produced).  On the
+        device the id bitsets answer (engine/device_exec.py PreparedDistinct); everywhere else --
+        CPU, no native code, hashed keys, bit matrices beyond the cap -- torch.unique over the packed
+        (group, id) pairs does (ops/reference.py distinct_counts).  Returns the tiers the device
+        used ("lds", "global", joined by commas), or None."""
+        if not prog.distincts:
+            return None
+        gid_order = np.asarray(cols["__gid__"], dtype=np.int64)
+        fused = self._distinct_fused(prog)
+        if fused is not None:
+            for (name, _, _, _), res in zip(prog.distincts, fused):
+                ok = (gid_order >= 0) & (gid_order < len(res))
+                cols[name] = np.where(ok, res[np.clip(gid_order, 0, max(0, len(res) - 1))], 0).astype(np.int64)
+            return ",".join(self._distinct_prep.tiers)
+        from ..ops.reference import _rows, compute_keys, distinct_counts, eval_bexpr
+        from .lower import column_tensor, distinct_null_id
+
+        ds = self.ds
+        rows = _rows(prog) if not prog.empty else torch.zeros(0, dtype=torch.int64, device=ds.device)
+        if rows.numel():
+            rows = rows[eval_bexpr(prog, prog.bexpr, rows)]
+        keys = compute_keys(prog, rows)
+        for name, col, filt, _ in prog.distincts:
+            r, k = rows, keys
+            if filt is not None and rows.numel():
+                keep = eval_bexpr(prog, filt, rows)
+                r, k = rows[keep], keys[keep]
+            dic = ds.dims[col].dictionary
+            gids, cnt = distinct_counts(k, column_tensor(ds, col)[r], len(dic), distinct_null_id(dic))
+            gids, cnt = gids.cpu().numpy(), cnt.cpu().numpy().astype(np.int64)
+            at = np.clip(np.searchsorted(gids, gid_order), 0, max(0, len(gids) - 1))
+            cols[name] = np.where(gids[at] == gid_order, cnt[at], 0).astype(np.int64) if len(gids) else \
+                np.zeros(len(gid_order), dtype=np.int64)
+        return None
+
+    def _distinct_fused(self, prog: ScanProgram) -> Optional[list]:
+        """Per distinctCount aggregator its counts [G] from the device bitsets, or None where they
+        do not apply (CPU, hashed or ineligible keys, a bit matrix beyond the cap, an empty shard)."""
+        if prog.empty or self.ds.device.type != "cuda" or not self.engine.use_native:
+            return None
+        dp = self.__dict__.get("_distinct_prep")
+        if dp is None:
+            try:
+                from .device_exec import PreparedDistinct
+
+                dp = PreparedDistinct(prog, prog.distincts)
+            except RuntimeError:
+                dp = False
+            self._distinct_prep = dp
+        if dp is False:
+            return None
+        return dp.count()
 
     # ------------------------------------------------------------------ post processing
     def _post(self, prog: ScanProgram, cols: Dict[str, np.ndarray]) -> QueryResult:

@@ -331,7 +331,7 @@ class KeyComp:
 @dataclass
 class AggOut:
     name: str
-    kind: str                     # count|sum_i|sum_f|sum_fx|min_i|max_i|min_f|max_f|hll|theta|quantile
+    kind: str                     # count|sum_i|sum_f|sum_fx|min_i|max_i|min_f|max_f|hll|theta|quantile|distinct
     slot: int = -1
     slot2: int = -1               # sum_fx: fraction slot (value = slot + slot2 * 2^-32)
     hll_index: int = -1
@@ -370,6 +370,8 @@ class ScanProgram:
     thetas: List[Tuple[str, str, int]] = field(default_factory=list)  # (name, column, size)
     # order statistics: (name, column, fractions, interpolate)
     quantiles: List[Tuple[str, str, Tuple[float, ...], bool]] = field(default_factory=list)
+    # exact distinct counts: (name, dimension, the aggregator's own filter or None, its fops span)
+    distincts: List[Tuple[str, str, Any, Tuple[int, int]]] = field(default_factory=list)
     luts: Dict[str, torch.Tensor] = field(default_factory=dict)       # dim -> f64 value per dictionary id
     lut_ptrs: Dict[float, torch.Tensor] = field(default_factory=dict)  # E_LUT operand -> its table
     # grouping keys functionally determined by a packed key: (key, index of determinant in keys,
@@ -387,10 +389,10 @@ class ScanProgram:
 
     @property
     def needs_rows(self) -> bool:
-        """Some aggregator reads the selected rows themselves (theta KMV, order statistics), not an
-        accumulator: strategies that keep only accumulators decline, the executor answers it after
-        the scan (engine/executor.py _theta / _quantile)."""
-        return bool(self.thetas or self.quantiles)
+        """Some aggregator reads the selected rows themselves (theta KMV, order statistics, exact
+        distinct counts), not an accumulator: strategies that keep only accumulators decline, the
+        executor answers it after the scan (engine/executor.py _theta / _quantile / _distinct)."""
+        return bool(self.thetas or self.quantiles or self.distincts)
 
     @property
     def nhll_total(self) -> int:
@@ -1335,6 +1337,16 @@ class Lowerer:
             prog.quantiles.append((a.name, a.fieldName, fr, bool(a.interpolate)))
             prog.aggs.append(AggOut(a.name, "quantile", combine="quantile"))
             return
+        if isinstance(a, S.DistinctCountAggregationSpec):
+            if self.world is not None and self.world.distributed:
+                # (every rank would count over its own shard: the bitsets are OR-mergeable but not
+                # reduced across ranks yet -- the SQL layer keeps its two-level plan there)
+                raise LoweringError("distinctCount aggregators are not answered across ranks")
+            if a.fieldName not in ds.dims:
+                raise LoweringError(f"distinctCount over {a.fieldName!r}: not a dimension")
+            prog.distincts.append((a.name, a.fieldName, filt, (0, 0)))
+            prog.aggs.append(AggOut(a.name, "distinct", out_type="long", combine="distinct"))
+            return
         raise LoweringError(f"unsupported aggregator {type(a).__name__}")
 
     def _emit_expr(self, prog: ScanProgram, ast, mapping: Dict[str, str]) -> List[tuple]:
@@ -1597,6 +1609,12 @@ class Lowerer:
                     if dep > D.STACK_DEPTH:
                         raise LoweringError("aggregator filter too deep")
                     d["filt_off"], d["filt_len"] = off, len(prog.fops) - off
+            for i, (name, col, f, _) in enumerate(prog.distincts):
+                if f is not None:  # (evaluated by the distinct producer: engine/device_exec.py)
+                    off = len(prog.fops)
+                    if self.emit_filter(prog, f) > D.STACK_DEPTH:
+                        raise LoweringError("aggregator filter too deep")
+                    prog.distincts[i] = (name, col, f, (off, len(prog.fops) - off))
             for d in prog.aops:
                 if d["expr"] is not None:
                     d["expr_off"] = len(prog.eops)
@@ -1665,6 +1683,13 @@ class Lowerer:
         self.emit_main_filter(prog, bexpr)
         self.pick_zones(prog, bexpr)
         return prog
+
+
+def distinct_null_id(dic) -> int:
+    """The dictionary id that stands for NULL (the null entry, else the ``""`` entry), or -1."""
+    if dic.has_null:
+        return int(dic.lookup(None))
+    return int(dic.lookup("")) if dic.vtype == "string" else -1
 
 
 FIX_ONE = float(1 << 32)  # fixed-point unit of deterministic float sums (AggOut.kind sum_fx)

@@ -23,6 +23,7 @@
 #include "post_scan.h"
 #include "quantile.h"
 #include "dict_match.h"
+#include "distinct.h"
 
 namespace sdo {
 template <int U>
@@ -106,6 +107,16 @@ __global__ void qsel_final_kernel(QselState s, int nfrac, int is_f64, double div
 template <bool FOLD>
 __global__ void dict_match_kernel(const uint8_t* __restrict__ heap, const uint32_t* __restrict__ off, uint32_t n,
                                   DmProgram prog, uint64_t* __restrict__ out, uint64_t* __restrict__ nonascii);
+// distinct.hip (shapes: distinct.h)
+__global__ void dcount_lds_regions_kernel(const uint32_t* recs, int rw, int voff, const uint32_t* seg_lo,
+                                          const uint32_t* seg_hi, int64_t nseg, uint32_t G, uint32_t D, uint32_t Wg,
+                                          uint32_t* state);
+__global__ void dcount_global_regions_kernel(const uint32_t* recs, int rw, int voff, const uint32_t* seg_lo,
+                                             const uint32_t* seg_hi, int64_t nseg, uint32_t G, uint32_t D, uint32_t Wg,
+                                             uint32_t* state);
+template <bool WAVE_ROW>
+__global__ void dcount_count_kernel(const uint32_t* __restrict__ state, uint32_t G, uint32_t Wg, int64_t null_id,
+                                    int64_t* __restrict__ out);
 // p2p.hip (P2PArgs: p2p.h)
 __global__ void p2p_merge_kernel(P2PArgs a);
 }  // namespace sdo
@@ -954,6 +965,52 @@ static void qsel_select(uint64_t recs, int rw, int voff, uint64_t seg_lo, uint64
 }
 
 // ---------------------------------------------------------------------------------------------
+// Exact COUNT(DISTINCT) over a distinct producer's chunk-region records (distinct.hip): record = u32
+// group key, then one u32 dictionary id per counted column; the counted column's id is word `voff`.
+// `state` is the [G][ceil(D / 32)] u32 bit matrix, `out` the [G] int64 counts without bit `null_id`.
+// tier 0: per-workgroup LDS copies of the matrix (G x Wg <= DCOUNT_LDS_WORDS), 1: test-then-set in HBM.
+static void dcount(uint64_t recs, int rw, int voff, uint64_t seg_lo, uint64_t seg_hi, int64_t nseg, int64_t G,
+                   int64_t D, int tier, int64_t null_id, uint64_t state, uint64_t out, uint64_t stream) {
+  if (G <= 0 || D <= 0 || D > 0x7fffffff) throw std::invalid_argument("dcount: groups / dictionary size");
+  if (rw < 2 || voff < 1 || voff >= rw) throw std::invalid_argument("dcount: record layout");
+  if (nseg < 0 || null_id < -1 || null_id >= D || !state || !out) throw std::invalid_argument("dcount: arguments");
+  const int64_t Wg = (D + 31) / 32;
+  const int64_t nw = G * Wg;
+  if (G > 0x7fffffff || nw >= ((int64_t)1 << 31)) throw std::invalid_argument("dcount: state beyond 2^31 words");
+  if (tier != 0 && tier != 1) throw std::invalid_argument("dcount: tier");
+  if (tier == 0 && nw > sdo::DCOUNT_LDS_WORDS) throw std::invalid_argument("dcount: state too large for LDS");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(sdo::qsel_clear_kernel, dim3(grid_for(nw, 256, 4096)), dim3(256), 0, s, (uint32_t*)state, nw);
+  check(hipGetLastError(), "dcount clear launch");
+  if (nseg > 0 && tier == 0) {
+    // Every workgroup clears and flushes all nw words whatever it read, so a workgroup should own at
+    // least 8 record slots per state word (then clear + flush stay under a quarter of its LDS
+    // traffic); never more workgroups than regions, and at most 1,024 (two rounds of the two 64 KiB
+    // workgroups a CU holds), the bound the quantile histograms use for the same flush pattern.
+    const int64_t want = nseg * (int64_t)sdo::DCOUNT_REGION / (8 * nw);
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, std::min<int64_t>(nseg, 1024)));
+    hipLaunchKernelGGL(sdo::dcount_lds_regions_kernel, dim3(grid), dim3(256), (size_t)nw * 4, s, (const uint32_t*)recs,
+                       rw, voff, (const uint32_t*)seg_lo, (const uint32_t*)seg_hi, nseg, (uint32_t)G, (uint32_t)D,
+                       (uint32_t)Wg, (uint32_t*)state);
+    check(hipGetLastError(), "dcount_lds_regions_kernel launch");
+  } else if (nseg > 0) {
+    const unsigned grid = (unsigned)std::min<int64_t>(nseg, 4096);
+    hipLaunchKernelGGL(sdo::dcount_global_regions_kernel, dim3(grid), dim3(256), 0, s, (const uint32_t*)recs, rw, voff,
+                       (const uint32_t*)seg_lo, (const uint32_t*)seg_hi, nseg, (uint32_t)G, (uint32_t)D, (uint32_t)Wg,
+                       (uint32_t*)state);
+    check(hipGetLastError(), "dcount_global_regions_kernel launch");
+  }
+  if (Wg <= sdo::DCOUNT_WAVE_ROW_WORDS) {
+    hipLaunchKernelGGL(sdo::dcount_count_kernel<true>, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, s,
+                       (const uint32_t*)state, (uint32_t)G, (uint32_t)Wg, null_id, (int64_t*)out);
+  } else {
+    hipLaunchKernelGGL(sdo::dcount_count_kernel<false>, dim3((unsigned)G), dim3(256), 0, s, (const uint32_t*)state,
+                       (uint32_t)G, (uint32_t)Wg, null_id, (int64_t*)out);
+  }
+  check(hipGetLastError(), "dcount_count_kernel launch");
+}
+
+// ---------------------------------------------------------------------------------------------
 // LIKE / contains / fragment over a dictionary's device text heap (dict_match.hip): bit e of `out`
 // says entry e matches `program` (a packed DmProgram); when the program folds case, bit e of
 // `nonascii` says entry e holds a byte >= 0x80 (the host re-evaluates those).  `heap` is 16-byte
@@ -1253,6 +1310,7 @@ PYBIND11_MODULE(_sdo_native, m) {
   m.def("theta_select_regions", &theta_select_regions);
   m.def("qsel_stats", &qsel_stats);
   m.def("qsel_select", &qsel_select);
+  m.def("dcount", &dcount);
   m.def("dict_match", &dict_match);
   m.def("dict_match_layout", &dict_match_layout);
   m.def("part_agg", &part_agg);

@@ -103,7 +103,8 @@ enum AKind : int32_t {
   A_ROWID = 10,      // emit producers: the row id as a record field (JIT only)
   A_HLL_CODE = 11,   // HLL over a code column: u16 (bucket << 5 | rho) per row (segment/hllcode.py)
   A_THETA = 12,      // theta producers: the 62-bit KMV hash of the column's value (JIT only)
-  A_QVAL = 13        // quantile producers: the column's value as an order-preserving u64 (JIT only)
+  A_QVAL = 13,       // quantile producers: the column's value as an order-preserving u64 (JIT only)
+  A_DISTINCT = 14    // distinct producers: the dimension's dictionary id, one u32 word (JIT only)
 };
 // accumulator slot update ops
 enum SlotOp : int32_t { S_SUM_I = 0, S_SUM_F = 1, S_MIN_I = 2, S_MAX_I = 3 };

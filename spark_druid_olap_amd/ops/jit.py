@@ -128,6 +128,9 @@ def part_fields(prog, cols=None) -> List[Tuple[int, int]]:
         if kind == D.A_QVAL:
             out.append((a["slot"], 2))  # ordered u64 value (quantile producers, engine/device_exec.py PreparedQuantile)
             continue
+        if kind == D.A_DISTINCT:
+            out.append((a["slot"], 1))  # u32 dictionary id (distinct producers, engine/device_exec.py PreparedDistinct)
+            continue
         w = 2
         if kind in (D.A_SUM_I, D.A_MIN_I, D.A_MAX_I) and not a.get("expr") and a.get("col") in cols:
             c = cols[a["col"]]
@@ -600,6 +603,8 @@ class _Gen:
             val = f"v{ai}_[u]"
             if a["kind"] == D.A_COUNT:
                 val = f"({cond} ? 1LL : 0LL)" if cond else "1LL"
+            elif a["kind"] == D.A_DISTINCT and cond:
+                val = f"({cond} ? {val} : -1LL)"  # (all ones: no dictionary id, the bitset kernels skip it)
             elif cond:
                 val = f"({cond} ? {val} : (int64_t){_lit(p.slots[slot][1])})"
             if width == 1:
@@ -777,6 +782,8 @@ class _Gen:
                     c = self.cols[a["col"]]
                     sv = f"f2ord({self.dval(a['col'])})" if c.flt else f"(int64_t)({self.ival(a['col'])})"
                     val = f"(int64_t)((uint64_t)({sv}) ^ 0x8000000000000000ull)"
+                elif kind == D.A_DISTINCT:
+                    val = self.ival(a["col"])  # the row's dictionary id (ops/csrc/distinct.hip)
                 elif kind == D.A_COUNT:
                     val = "1LL"
                 elif kind == D.A_SUM_X:

@@ -392,6 +392,17 @@ def run_reference(prog, sparse: Optional[bool] = None):
     return Partials("dense", acc, None, hlls)
 
 
+def distinct_counts(keys: torch.Tensor, ids: torch.Tensor, D: int, null_id: int = -1):
+    """Exact COUNT(DISTINCT) by sorting: (group keys ascending, distinct ids per group) of the
+    (group key, dictionary id) pairs, ids in [0, D), the id ``null_id`` not counted -- the
+    reference of ops/csrc/distinct.hip and the engine's answer wherever the bitsets do not apply."""
+    if null_id >= 0:
+        keep = ids != null_id
+        keys, ids = keys[keep], ids[keep]
+    pairs = torch.unique(keys.to(torch.int64) * int(D) + ids.to(torch.int64))
+    return torch.unique_consecutive(torch.div(pairs, int(D), rounding_mode="floor"), return_counts=True)
+
+
 def run_reference_mask(prog) -> torch.Tensor:
     """Row ids passing the filter (select queries)."""
     dev = prog.ds.device

@@ -514,6 +514,17 @@ class QuantilesAggregationSpec(Spec, _Decodable):
     type: str = "quantiles"
 
 
+@_register("aggregation", "distinctCount")
+@dataclass
+class DistinctCountAggregationSpec(Spec, _Decodable):
+    """Exact number of distinct non-null values of one dimension among the selected rows (Druid's
+    ``distinctCount`` extension: a bitmap of dictionary ids per group).  This engine's null is the
+    ``""`` dictionary entry, as for ``count(dim)``; the result is a long."""
+    name: str
+    fieldName: str
+    type: str = "distinctCount"
+
+
 # ============================================================================ post aggregations
 @_register("postagg", "fieldAccess")
 @dataclass

@@ -478,7 +478,7 @@ class Session:
             if not getattr(sq, "_planned", False):
                 object.__setattr__(sq, "query", self._physical(sq.query, rw))
                 object.__setattr__(sq, "_planned", True)
-        opt = optimize(analyzed, self.conf)
+        opt = optimize(analyzed, self.conf, rw.direct_distinct)
         for m in self.modules:
             for rule in getattr(m, "logical_rules", []) or []:
                 opt = rule(opt, self) or opt

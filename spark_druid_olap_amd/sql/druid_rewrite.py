@@ -88,6 +88,12 @@ def _short(n: str) -> str:
     return n.split(".")[-1].lower()
 
 
+# Exact COUNT(DISTINCT dim) pushed as a ``distinctCount`` aggregator (ops/csrc/distinct.hip) instead
+# of the optimizer's two-level rewrite.  Off: every statement keeps the two-level plan (tests and
+# tools/distinct_probe.py compare the two in one process).
+DIRECT_DISTINCT = True
+
+
 class DruidRewriter:
     def __init__(self, session):
         self.session = session
@@ -106,6 +112,26 @@ class DruidRewriter:
         except NotPushable as ex:
             self.log.append(f"{type(p).__name__}: not pushed ({ex})")
             return None
+
+    def direct_distinct(self, agg: P.Aggregate) -> bool:
+        """The optimizer's question (sql/optimizer.py _distinct_rewrite): does this aggregate, exact
+        COUNT(DISTINCT) calls included, push as ONE Druid query as it stands?  Only then is it kept
+        from the two-level rewrite -- every other statement plans as before."""
+        eng = self.session.engine
+        mode = str(self.conf.typed("spark.sparklinedata.druid.distinctCount.pushdown")).lower()
+        if not DIRECT_DISTINCT or mode == "off" or self.approx_distinct or eng.world.distributed or not eng.use_native:
+            return False
+        if mode != "all":
+            # the reference's plan shapes are kept (its suites pin the number of Druid queries): a
+            # statement with ordinary aggregates or several distinct arguments stays two queries and a join
+            dist = [a.child for a in agg.aggs if a.child.name == "count" and a.child.distinct]
+            if len(dist) != len(agg.aggs) or len({tuple(x.key() for x in c.args) for c in dist}) != 1:
+                return False
+        n = len(self.log)
+        try:
+            return self._try(self._aggregate, agg) is not None
+        finally:
+            del self.log[n:]
 
     def _top_down(self, p: P.Plan) -> P.Plan:
         # structural rules first: they need the original Project/Filter/Join chains below them
@@ -663,7 +689,7 @@ class DruidRewriter:
             call = A.Call(call.name, tuple(pf.sub(x) for x in call.args), call.distinct)
             if not is_deterministic(call):
                 raise NotPushable(f"non-deterministic aggregate {call.sql()}")
-            parts, combine = self._agg_spec(pf, call, names)
+            parts, combine = self._agg_spec(pf, call, names, direct=agg.grouping_sets is None)
             prefs = []
             for part in parts:
                 spec_, t = part[0], part[1]
@@ -703,6 +729,7 @@ class DruidRewriter:
                                     final[rid])
         q = S.GroupByQuerySpec(info.ds_name, dims, None, None, S.Granularity.parse("all"), filt, aggs, None,
                                intervals)
+        self._check_distinct_state(q, ds)
         method = {}
         dq = P.DruidQuery(pf.table, q, columns, drefs, {"groupby": True, "noop_conds": pf.noop_conds,
                                                          "historical": self._historical(pf, q, method)})
@@ -814,7 +841,43 @@ class DruidRewriter:
         return None
 
     # -- aggregates ------------------------------------------------------------------------------
-    def _agg_spec(self, pf: PF, call: A.Call, names: "_Names"):
+    def _check_distinct_state(self, q, ds) -> None:
+        """A pushed ``distinctCount`` keeps a [groups][dictionary size] bit matrix: the statement is
+        pushed in this form only where every matrix fits the device tiers
+        (engine/device_exec.py distinct_tier); NotPushable otherwise (the two-level plan runs)."""
+        dcs = [a for a in q.aggregations if isinstance(a, S.DistinctCountAggregationSpec)]
+        if not dcs:
+            return
+        from ..engine.device_exec import distinct_tier
+        from ..engine.lower import Lowerer, LoweringError
+
+        try:
+            prog = Lowerer(ds, world=self.session.engine.world).lower_aggregate(
+                q.intervals, q.filter, q.dimensions, q.granularity, q.aggregations)
+        except LoweringError as ex:
+            raise NotPushable(f"distinctCount: {ex}")
+        for a in dcs:
+            if distinct_tier(prog.G, len(ds.dims[a.fieldName].dictionary)) is None:
+                raise NotPushable(f"distinctCount({a.fieldName}): {prog.G} groups x "
+                                  f"{len(ds.dims[a.fieldName].dictionary)} values exceed the bitset cap")
+
+    def _direct_distinct_spec(self, pf: PF, call: A.Call, names: "_Names", rolled: bool):
+        """count(DISTINCT x) -> a ``distinctCount`` aggregator, or None: exact mode, the native GPU
+        engine on one rank, a datasource that is not rolled up, and one argument that is a plain
+        reference to a non-time dimension."""
+        eng = self.session.engine
+        ds = pf.table.info.datasource
+        if not DIRECT_DISTINCT or self.approx_distinct or rolled or getattr(ds, "rollup", False) \
+                or eng.world.distributed or not eng.use_native or ds.device.type != "cuda":
+            return None
+        if len(call.args) != 1 or not isinstance(call.args[0], A.Ref):
+            return None
+        c = self._column(pf, call.args[0])
+        if c.kind != "dimension" or c.is_time or c.druid_column not in ds.dims:
+            return None
+        return [(S.DistinctCountAggregationSpec(names.agg(), c.druid_column), "bigint")], lambda rs: rs[0]
+
+    def _agg_spec(self, pf: PF, call: A.Call, names: "_Names", direct: bool = True):
         info = pf.table.info
         ds = info.datasource
         n = call.name
@@ -839,6 +902,9 @@ class DruidRewriter:
             return [count_spec()], lambda rs: rs[0]
         if (n == "count" and call.distinct) or n == "approx_count_distinct":
             if n == "count" and not self.approx_distinct:
+                dc = self._direct_distinct_spec(pf, call, names, rolled) if direct else None
+                if dc is not None:
+                    return dc
                 raise NotPushable("exact COUNT(DISTINCT) (rewritten to a two-level aggregate)")
             if not info.options.pushHLLTODruid:
                 raise NotPushable("pushHLLTODruid is false")

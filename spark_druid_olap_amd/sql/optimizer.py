@@ -23,12 +23,15 @@ from . import plan as P
 from .functions import constant_fold, is_deterministic, typeof
 
 
-def optimize(plan: P.Plan, conf=None) -> P.Plan:
+def optimize(plan: P.Plan, conf=None, keep_distinct=None) -> P.Plan:
+    """``keep_distinct(aggregate) -> bool``: the Druid rewrite answers this aggregate's exact
+    COUNT(DISTINCT) calls inside one pushed query (``distinctCount`` aggregators,
+    sql/druid_rewrite.py ``direct_distinct``), so it is left as written."""
     approx = bool(conf.typed("spark.sparklinedata.druid.approxCountDistinct")) if conf is not None else False
     p = plan.transform_up(_simplify_filter)
     p = p.transform_up(_sum_of_literal)
     if not approx:
-        p = p.transform_up(_distinct_rewrite)
+        p = p.transform_up(lambda x: _distinct_rewrite(x, keep_distinct))
     p = _push_down_all(p)
     p = _push_down_all(_reorder_joins(p))
     q = p.transform_up(_push_gb)
@@ -100,11 +103,13 @@ def _has_druid(p: P.Plan) -> bool:
     return any(isinstance(x, P.TableScan) and x.table.kind == "druid" for x in p.walk())
 
 
-def _distinct_rewrite(p: P.Plan):
+def _distinct_rewrite(p: P.Plan, keep=None):
     if not isinstance(p, P.Aggregate) or p.grouping_sets is not None:
         return None
     dist = [a for a in p.aggs if a.child.name == "count" and a.child.distinct]
     if not dist or not _has_druid(p.child):
+        return None
+    if keep is not None and keep(p):
         return None
     regular = [a for a in p.aggs if not (a.child.name == "count" and a.child.distinct)]
     if any(a.child.distinct for a in regular):
