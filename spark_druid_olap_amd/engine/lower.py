@@ -25,7 +25,7 @@ from ..ops import desc as D
 from ..query import joda
 from ..query import spec as S
 from ..query.granularity import Granularity, bucket_start_from_value, bucket_value
-from ..query.intervals import Interval, parse_iso_ms
+from ..query.intervals import Interval, parse_iso_ms, tz_offset_ms  # noqa: F401 (re-exported)
 from ..query.jsfunc import JSError, compile_function, jsagg_to_expr, parse_expr
 from ..segment.datasource import CHUNK_ROWS, DataSource, dtype_code
 from ..segment.dictionary import Dictionary
@@ -276,28 +276,26 @@ def extraction_callable(fn) -> Callable[[Any], Any]:
     raise LoweringError(f"unsupported extraction function {type(fn).__name__}")
 
 
+def _exact_number(v):
+    """A filter bound as an exact Fraction (ints and decimal strings are not rounded through a
+    float); +-inf and NaN come back as the float."""
+    from fractions import Fraction
+
+    if isinstance(v, (bool, int, np.integer)):
+        return Fraction(int(v))
+    if isinstance(v, str):
+        try:
+            return Fraction(v.strip())
+        except (ValueError, ZeroDivisionError):
+            pass
+    x = float(v)
+    return Fraction(x) if math.isfinite(x) else x
+
+
 def _druid_str(v) -> str:
     if isinstance(v, float) and v.is_integer():
         return str(int(v))
     return str(v)
-
-
-def tz_offset_ms(tz: Optional[str], at_ms: int = 0) -> int:
-    if tz is None or tz.upper() in ("UTC", "Z", "GMT", "ETC/UTC"):
-        return 0
-    m = re.match(r"^(?:UTC|GMT)?([+-])(\d{1,2}):?(\d{2})?$", tz)
-    if m:
-        sgn = -1 if m.group(1) == "-" else 1
-        return sgn * (int(m.group(2)) * 60 + int(m.group(3) or 0)) * 60_000
-    try:
-        import datetime as _dt
-        from zoneinfo import ZoneInfo
-
-        z = ZoneInfo(tz)
-        dt = _dt.datetime.fromtimestamp(at_ms / 1000.0, tz=_dt.timezone.utc).astimezone(z)
-        return int(dt.utcoffset().total_seconds() * 1000)
-    except Exception:
-        return 0
 
 
 # =================================================================================== program
@@ -689,20 +687,33 @@ class Lowerer:
         m = self.ds.metrics[name]
         scale = 10 ** m.scale if m.kind == "decimal" else 1
         if isinstance(f, S.SelectorFilterSpec):
-            v = float(f.value)
             if m.is_integral:
-                x = v * scale
-                if x != math.floor(x):
+                x = _exact_number(f.value)
+                if isinstance(x, float):  # +-inf / NaN never equal a stored integer
+                    return FALSE
+                x *= scale
+                if x.denominator != 1 or not D.INT64_MIN <= x <= D.INT64_MAX:
                     return FALSE
                 return ("int", name, int(x), int(x))
+            v = float(f.value)
             return ("flt", name, v, v, 0)
         if isinstance(f, S.BoundFilterSpec):
-            lo = None if f.lower is None else float(f.lower)
-            hi = None if f.upper is None else float(f.upper)
             if m.is_integral:
+                # integral bounds stay exact (a float would round 2^63 - 1 up to 2^63 and anything
+                # above 2^53 to a neighbour) and are clamped to what FOp's int64 fields hold
+                lo = None if f.lower is None else _exact_number(f.lower)
+                hi = None if f.upper is None else _exact_number(f.upper)
+                if (isinstance(lo, float) and not lo < 0) or (isinstance(hi, float) and not hi > 0):
+                    return FALSE  # lower bound +inf / NaN, upper bound -inf / NaN
+                lo = None if isinstance(lo, float) else lo
+                hi = None if isinstance(hi, float) else hi
                 ilo = -(2 ** 62) if lo is None else (math.floor(lo * scale) + 1 if f.lowerStrict else math.ceil(lo * scale))
                 ihi = 2 ** 62 if hi is None else (math.ceil(hi * scale) - 1 if f.upperStrict else math.floor(hi * scale))
-                return ("int", name, int(ilo), int(ihi))
+                if ilo > D.INT64_MAX or ihi < D.INT64_MIN:
+                    return FALSE
+                return ("int", name, max(int(ilo), int(D.INT64_MIN)), min(int(ihi), int(D.INT64_MAX)))
+            lo = None if f.lower is None else float(f.lower)
+            hi = None if f.upper is None else float(f.upper)
             flags = (1 if f.lowerStrict else 0) | (2 if f.upperStrict else 0)
             return ("flt", name, -math.inf if lo is None else lo, math.inf if hi is None else hi, flags)
         raise LoweringError(f"unsupported metric filter {type(f).__name__}")

@@ -151,8 +151,8 @@ def _torch_eval(n, pmap: Dict[str, str], cols: Dict[str, DeviceColumn]) -> torch
     a, b = _torch_eval(n[1], pmap, cols), _torch_eval(n[2], pmap, cols)
     if a.device != b.device:
         a, b = a.to(b.device) if a.dim() == 0 else a, b.to(a.device) if b.dim() == 0 else b
-    fns = {"add": torch.add, "sub": torch.sub, "mul": torch.mul, "div": torch.div, "min": torch.minimum,
-           "max": torch.maximum, "mod": torch.fmod, "pow": torch.pow}
+    fns = {"add": torch.add, "sub": torch.sub, "mul": torch.mul, "div": torch.div, "min": torch.fmin,
+           "max": torch.fmax, "mod": torch.fmod, "pow": torch.pow}
     if k not in fns:
         raise LoweringError(f"nested expression operator {k}")
     return fns[k](a, b)

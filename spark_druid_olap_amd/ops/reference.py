@@ -148,6 +148,15 @@ def eval_bexpr(prog, x, rows: torch.Tensor) -> torch.Tensor:
     raise ValueError(k)
 
 
+def _sqrt(x: torch.Tensor) -> torch.Tensor:
+    """Correctly rounded f64 square root (IEEE 754, like the device's): torch's vectorized CPU
+    sqrt is 1 ulp off on some hosts (sqrt(0.5), sqrt(2)), numpy's is not."""
+    if x.is_cuda:
+        return torch.sqrt(x)
+    with np.errstate(invalid="ignore"):
+        return torch.from_numpy(np.sqrt(x.contiguous().numpy()))
+
+
 def _ast_values(prog, n, rows: torch.Tensor) -> torch.Tensor:
     """f64 value per row of an expression AST (expression filters; same value model as the
     device VM: metrics with decimal scale, dimensions through their f64 dictionary table)."""
@@ -174,14 +183,14 @@ def _ast_values(prog, n, rows: torch.Tensor) -> torch.Tensor:
         return v
     if k in ("neg", "abs", "floor", "ceil", "sqrt", "log", "exp"):
         a = _ast_values(prog, n[1], rows)
-        return {"neg": torch.neg, "abs": torch.abs, "floor": torch.floor, "ceil": torch.ceil, "sqrt": torch.sqrt,
+        return {"neg": torch.neg, "abs": torch.abs, "floor": torch.floor, "ceil": torch.ceil, "sqrt": _sqrt,
                 "log": torch.log, "exp": torch.exp}[k](a)
     a, b = _ast_values(prog, n[1], rows), _ast_values(prog, n[2], rows)
     if k == "pmod":
         m = torch.fmod(a, b)
         return torch.where(m < 0, torch.fmod(m + b, b), m)
-    return {"add": torch.add, "sub": torch.sub, "mul": torch.mul, "div": torch.div, "min": torch.minimum,
-            "max": torch.maximum, "mod": torch.fmod, "pow": torch.pow}[k](a, b)
+    return {"add": torch.add, "sub": torch.sub, "mul": torch.mul, "div": torch.div, "min": torch.fmin,
+            "max": torch.fmax, "mod": torch.fmod, "pow": torch.pow}[k](a, b)
 
 
 def _time_field(ms: torch.Tensor, kc) -> torch.Tensor:
@@ -282,7 +291,7 @@ def _expr_values(prog, eops, rows: torch.Tensor) -> torch.Tensor:
         elif op == D.E_ABS:
             st[-1] = st[-1].abs()
         elif op in (D.E_FLOOR, D.E_CEIL, D.E_SQRT, D.E_LOG, D.E_EXP):
-            st[-1] = {D.E_FLOOR: torch.floor, D.E_CEIL: torch.ceil, D.E_SQRT: torch.sqrt, D.E_LOG: torch.log,
+            st[-1] = {D.E_FLOOR: torch.floor, D.E_CEIL: torch.ceil, D.E_SQRT: _sqrt, D.E_LOG: torch.log,
                       D.E_EXP: torch.exp}[op](st[-1])
         elif op in (D.E_MOD, D.E_PMOD, D.E_POW):
             b = st.pop()
@@ -298,7 +307,7 @@ def _expr_values(prog, eops, rows: torch.Tensor) -> torch.Tensor:
             b = st.pop()
             a = st.pop()
             st.append({D.E_ADD: a + b, D.E_SUB: a - b, D.E_MUL: a * b, D.E_DIV: a / b,
-                       D.E_MIN: torch.minimum(a, b), D.E_MAX: torch.maximum(a, b)}[op])
+                       D.E_MIN: torch.fmin(a, b), D.E_MAX: torch.fmax(a, b)}[op])
     return st[-1]
 
 

@@ -10,7 +10,7 @@ import re
 from dataclasses import dataclass
 from typing import Optional, Union
 
-from .intervals import civil_from_days, days_from_civil, parse_iso_ms
+from .intervals import civil_from_days, days_from_civil, parse_iso_ms, tz_offset_ms
 
 # TField codes (scan_desc.h)
 T_MS, T_SECOND, T_MINUTE, T_HOUR, T_DAY, T_WEEK, T_MONTH, T_QUARTER, T_YEAR = range(9)
@@ -129,6 +129,9 @@ class Granularity:
         if self.name == "duration":
             return {"type": "duration", "duration": self.period_ms, "origin": self.origin_ms}
         d = {"type": "period", "period": self._period_str()}
+        if self.tz_ms:
+            a = abs(self.tz_ms) // 60_000
+            d["timeZone"] = f"{'-' if self.tz_ms < 0 else '+'}{a // 60:02d}:{a % 60:02d}"
         return d
 
     def _period_str(self) -> str:
@@ -167,14 +170,15 @@ class Granularity:
             origin = g.get("origin", 0)
             if isinstance(origin, str):
                 origin = parse_iso_ms(origin)
+            tz = tz_offset_ms(g.get("timeZone"), int(origin or 0))  # Druid's period granularity zone (fixed offset)
             if yy == 1 and not any((mm, ww, dd, hh, mi, ss)):
-                return Granularity("period", 0, 0, calendar="year")
+                return Granularity("period", 0, 0, tz, calendar="year")
             if mm in (1, 3) and not any((yy, ww, dd, hh, mi, ss)):
-                return Granularity("period", 0, 0, calendar="month" if mm == 1 else "quarter")
+                return Granularity("period", 0, 0, tz, calendar="month" if mm == 1 else "quarter")
             if yy or mm:
                 raise ValueError(f"unsupported calendar period {p!r}")
             ms = ((((ww * 7 + dd) * 24 + hh) * 60 + mi) * 60 + ss) * 1000
-            return Granularity("period", ms, int(origin or 0))
+            return Granularity("period", ms, int(origin or 0), tz)
         raise ValueError(f"unknown granularity spec {g!r}")
 
 

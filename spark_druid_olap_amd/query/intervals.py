@@ -141,3 +141,21 @@ class QueryIntervals:
     def intervals(self) -> List[Interval]:
         i = self.current if self.current is not None else self.index_interval
         return [i if not i.empty else Interval(i.lo, i.lo)]
+
+
+def tz_offset_ms(tz: Optional[str], at_ms: int = 0) -> int:
+    if tz is None or tz.upper() in ("UTC", "Z", "GMT", "ETC/UTC"):
+        return 0
+    m = re.match(r"^(?:UTC|GMT)?([+-])(\d{1,2}):?(\d{2})?$", tz)
+    if m:
+        sgn = -1 if m.group(1) == "-" else 1
+        return sgn * (int(m.group(2)) * 60 + int(m.group(3) or 0)) * 60_000
+    try:
+        import datetime as _dt
+        from zoneinfo import ZoneInfo
+
+        z = ZoneInfo(tz)
+        dt = _dt.datetime.fromtimestamp(at_ms / 1000.0, tz=_dt.timezone.utc).astimezone(z)
+        return int(dt.utcoffset().total_seconds() * 1000)
+    except Exception:
+        return 0

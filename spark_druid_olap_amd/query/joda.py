@@ -223,7 +223,7 @@ def representative_ms(tfield: int, v: int) -> int:
     if tfield == T_DOW:
         return (days_from_civil(2001, 1, 1) + (v - 1)) * 86_400_000  # 2001-01-01 was a Monday
     if tfield == T_DOY:
-        return (days_from_civil(2001, 1, 1) + v - 1) * 86_400_000
+        return (days_from_civil(2000, 1, 1) + v - 1) * 86_400_000  # a leap year: day 366 exists
     if tfield == T_HOD:
         return v * 3_600_000
     if tfield == T_MOH:
