@@ -1485,7 +1485,7 @@ class PreparedEmit:
         ep = copy.copy(prog)
         ep.aops = [{"kind": D.A_ROWID, "col": -1, "expr": None, "filter": None, "slot": 0, "hll": -1}]
         ep.slots = [(D.S_SUM_I, 0)]
-        ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.packed = 0, [], [], [], [], {}
+        ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
         ep.presence_only = False
         self.prog = ep
         self.dev = prog.ds.device
@@ -1556,7 +1556,7 @@ def theta_producer_prog(prog: ScanProgram, cols: List[str]) -> ScanProgram:
     ep.aops = [{"kind": D.A_THETA, "col": ep.col(c), "expr": None, "filter": None, "slot": i, "hll": -1}
                for i, c in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(cols)
-    ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.packed = 0, [], [], [], [], {}
+    ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("theta: program not eligible")
@@ -1742,7 +1742,7 @@ def quantile_producer_prog(prog: ScanProgram, cols: List[str]) -> ScanProgram:
     ep.aops = [{"kind": D.A_QVAL, "col": ep.col(c), "expr": None, "filter": None, "slot": i, "hll": -1}
                for i, c in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(cols)
-    ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.packed = 0, [], [], [], [], {}
+    ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("quantile: program not eligible")
@@ -1754,7 +1754,52 @@ QSEL_GLOBAL_BITS = 8             # digit width when the state rows' bins live in
 QSEL_MAX_HIST_BYTES = 512 << 20
 
 
-class PreparedQuantile:
+class _QvalRecords:
+    """ONE JIT producer pass (ops/jit.py A_QVAL) that writes (u32 group key, ordered u64 value per
+    column of ``cols``) records of the selected rows into its chunk regions: what the quantile
+    select and the moment sums read.  ``what`` names the caller in the RuntimeErrors."""
+
+    def __init__(self, prog: ScanProgram, cols: List[str], max_g: int, what: str):
+        from .lower import lds_layout
+
+        ds = prog.ds
+        if prog.empty or not (0 < prog.G <= max_g):
+            raise RuntimeError(f"{what}: program not eligible")
+        self.cols = cols
+        ep = quantile_producer_prog(prog, self.cols)
+        self.prog, self.dev, self.G = ep, ds.device, int(prog.G)
+        self.jit = _jit_for(ep, D.M_PART, False, 1 << prog.hll_p)
+        if self.jit is None:
+            raise RuntimeError(f"{what}: no JIT kernel")
+        cache_off, wave_bytes, _, total = lds_layout(ep, 0, UNROLL, BLOCK // 64)
+        d = pack(ep, D.M_PART, 0, 0, 0, 0, 0, 0, 0, 0, 0, [], [], unroll=UNROLL, cache_off=cache_off,
+                 wave_bytes=wave_bytes)
+        self.nch = int(d[0]["total_chunks"])
+        self.grid = _grid(self.dev, self.nch, self.jit.lay.total, self.jit)
+        self.rw = 1 + 2 * len(self.cols)
+        cap = self.nch * D.CHUNK_ROWS
+        if cap * self.rw >= (1 << 32):
+            raise RuntimeError(f"{what}: shard too large for u32 offsets")
+        self.words = max(1, cap * self.rw)
+        self.seg_lo = (torch.arange(self.nch, dtype=torch.int64) * D.CHUNK_ROWS).to(torch.int32).to(self.dev)
+        self._d = d
+
+    def voff(self, col: str) -> int:
+        """Record word at which ``col``'s value starts."""
+        return 1 + 2 * self.cols.index(col)
+
+    def produce(self, nat, st, slab, pend) -> tuple:
+        """Launch the producer into ``slab`` (region ends into ``pend``); the region arguments the
+        record kernels take (recs, rw, ..., G) without the value offset."""
+        d = self._d.copy()
+        d[0]["part_recs"] = slab.recs1.data_ptr()
+        d[0]["part_counts"] = pend.data_ptr()
+        desc = _upload(d.view(np.uint8), self.dev)
+        nat.module_launch(self.jit.handle, desc.data_ptr(), int(self.grid), BLOCK, int(self.jit.lay.total), st)
+        return self.seg_lo.data_ptr(), pend.data_ptr(), self.nch, self.G
+
+
+class PreparedQuantile(_QvalRecords):
     """``quantiles`` aggregators pushed into the scan: ONE JIT producer pass (ops/jit.py A_QVAL)
     writes (u32 group key, ordered u64 value per distinct column) records of the selected rows into
     its chunk regions, and the per-group radix rank select (ops/csrc/quantile.hip) resolves every
@@ -1764,29 +1809,8 @@ class PreparedQuantile:
     metrics; G <= ``max_g``."""
 
     def __init__(self, prog: ScanProgram, quantiles: list, max_g: int):
-        from .lower import lds_layout
-
+        super().__init__(prog, sorted({c for _, c, _, _ in quantiles}), max_g, "quantile")
         ds = prog.ds
-        if prog.empty or not (0 < prog.G <= max_g):
-            raise RuntimeError("quantile: program not eligible")
-        self.cols = sorted({c for _, c, _, _ in quantiles})
-        ep = quantile_producer_prog(prog, self.cols)
-        self.prog, self.dev, self.G = ep, ds.device, int(prog.G)
-        self.jit = _jit_for(ep, D.M_PART, False, 1 << prog.hll_p)
-        if self.jit is None:
-            raise RuntimeError("quantile: no JIT kernel")
-        cache_off, wave_bytes, _, total = lds_layout(ep, 0, UNROLL, BLOCK // 64)
-        d = pack(ep, D.M_PART, 0, 0, 0, 0, 0, 0, 0, 0, 0, [], [], unroll=UNROLL, cache_off=cache_off,
-                 wave_bytes=wave_bytes)
-        self.nch = int(d[0]["total_chunks"])
-        self.grid = _grid(self.dev, self.nch, self.jit.lay.total, self.jit)
-        self.rw = 1 + 2 * len(self.cols)
-        cap = self.nch * D.CHUNK_ROWS
-        if cap * self.rw >= (1 << 32):
-            raise RuntimeError("quantile: shard too large for u32 offsets")
-        self.words = max(1, cap * self.rw)
-        self.seg_lo = (torch.arange(self.nch, dtype=torch.int64) * D.CHUNK_ROWS).to(torch.int32).to(self.dev)
-        self._d = d
         # per aggregator: (value word offset, fractions, interpolate, is double, decimal scale)
         self.sel = []
         for _, c, fr, interp in quantiles:
@@ -1794,7 +1818,7 @@ class PreparedQuantile:
             nr = self.G * len(fr) * (2 if interp else 1)
             if (nr << (QSEL_GLOBAL_BITS if nr * 16 > QSEL_LDS_BINS else 4)) * 4 > QSEL_MAX_HIST_BYTES:
                 raise RuntimeError("quantile: too many (group, rank) rows")
-            self.sel.append((1 + 2 * self.cols.index(c), tuple(fr), bool(interp), m.kind == "double",
+            self.sel.append((self.voff(c), tuple(fr), bool(interp), m.kind == "double",
                              int(m.scale) if m.kind == "decimal" else 0))
         self.plan = []  # (per aggregator of the last run: value width W, digit bits B, levels)
 
@@ -1819,11 +1843,7 @@ class PreparedQuantile:
         slab = PART_POOL.acquire(dev, self.words)
         out, self.plan = [], []
         try:
-            d = self._d.copy()
-            d[0]["part_recs"] = slab.recs1.data_ptr()
-            d[0]["part_counts"] = pend.data_ptr()
-            desc = _upload(d.view(np.uint8), dev)
-            nat.module_launch(self.jit.handle, desc.data_ptr(), int(self.grid), BLOCK, int(self.jit.lay.total), st)
+            self.produce(nat, st, slab, pend)
             # count / min / max / width depend on the column only: one stats pass per distinct column,
             # their widest-group widths read together (the only sync before the result copies)
             stats = {}
@@ -1866,6 +1886,69 @@ class PreparedQuantile:
         return out
 
 
+MOM_INT2, MOM_INT4, MOM_F64_SUM, MOM_F64_DEV = range(4)  # ops/csrc/moments.h MomMode
+MOM_TIERS = ("few", "lds", "global")                     # ... and MomTier
+
+
+class PreparedMoments(_QvalRecords):
+    """``variance`` aggregators pushed into the scan: the quantile producer's records (one pass for
+    all columns), then per distinct column the moment sums of ops/csrc/moments.hip and per
+    aggregator the finalise kernel.  Long / decimal metrics: ONE exact pass (n, sum x, digit sums of
+    x^2; two digits when the stored type is at most 32 bits wide, else four), bitwise reproducible.
+    Double metrics: a sum pass, the means, a pass over the deviations -- reproducible to a few ulp.
+    Nothing is read back before the result copy.  G <= ``max_g``."""
+
+    def __init__(self, prog: ScanProgram, moments: list, max_g: int):
+        super().__init__(prog, sorted({c for _, c, _ in moments}), max_g, "moments")
+        ds = prog.ds
+        # per distinct column: (value word offset, accumulation mode, decimal scale)
+        self.passes = {}
+        for c in self.cols:
+            m = ds.metrics[c]
+            if m.kind == "double":
+                mode = MOM_F64_SUM
+            else:
+                mode = MOM_INT2 if m.data.dtype.itemsize <= 4 else MOM_INT4
+            self.passes[c] = (self.voff(c), mode, int(m.scale) if m.kind == "decimal" else 0)
+        self.sel = [(c, int(ddof)) for _, c, ddof in moments]
+        self.tiers = []  # (per distinct column of the last run: the tier its first pass took)
+
+    def variances(self) -> list:
+        """Per aggregator its variances [G] (host float64; NaN where the group holds <= ddof rows)."""
+        nat, st = native.load(), native._stream(self.dev)
+        dev, G = self.dev, self.G
+        pend = torch.empty(max(1, self.nch), dtype=torch.int32, device=dev)
+        slab = PART_POOL.acquire(dev, self.words)
+        try:
+            regions = self.produce(nat, st, slab, pend)
+            states, self.tiers = {}, []
+            for c, (voff, mode, _) in self.passes.items():
+                a = torch.empty(G * (6 if mode == MOM_INT4 else 4 if mode == MOM_INT2 else 2), dtype=torch.int64,
+                                device=dev)
+                tier = nat.moments_accum(slab.recs1.data_ptr(), self.rw, voff, *regions, mode, -1, 0, a.data_ptr(), st)
+                b = None
+                if mode == MOM_F64_SUM:
+                    mean = torch.empty(G, dtype=torch.float64, device=dev)
+                    b = torch.empty(G * 2, dtype=torch.int64, device=dev)
+                    nat.moments_mean(a.data_ptr(), G, mean.data_ptr(), st)
+                    nat.moments_accum(slab.recs1.data_ptr(), self.rw, voff, *regions, MOM_F64_DEV, -1,
+                                      mean.data_ptr(), b.data_ptr(), st)
+                states[c] = (a, b)
+                self.tiers.append(MOM_TIERS[tier])
+            res = []
+            for c, ddof in self.sel:
+                _, mode, scale = self.passes[c]
+                a, b = states[c]
+                out = torch.empty(G, dtype=torch.float64, device=dev)
+                nat.moments_final(a.data_ptr(), b.data_ptr() if b is not None else 0, G,
+                                  MOM_F64_DEV if b is not None else mode, ddof, float(10 ** (2 * scale)),
+                                  out.data_ptr(), st)
+                res.append(out)
+            return [r.cpu().numpy() for r in res]
+        finally:
+            PART_POOL.release(slab)
+
+
 def distinct_producer_prog(prog: ScanProgram, cols: list) -> ScanProgram:
     """The scan program of a distinct producer: ``prog``'s filter, ranges and group key, one
     A_DISTINCT aggregator (the dimension's dictionary id, one record word) per (column, aggregator
@@ -1879,7 +1962,7 @@ def distinct_producer_prog(prog: ScanProgram, cols: list) -> ScanProgram:
     ep.aops = [{"kind": D.A_DISTINCT, "col": ep.col(c), "expr": None, "filter": None, "slot": i, "hll": -1,
                 "filt_off": off, "filt_len": n} for i, (c, (off, n)) in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(cols)
-    ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.packed = 0, [], [], [], [], {}
+    ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("distinct: program not eligible")

@@ -499,6 +499,7 @@ class PreparedQuery:
                 self._theta(self._full_prog, cols)
                 self._quantile(self._full_prog, cols)
                 tiers = self._distinct(self._full_prog, cols)
+                self._moments(self._full_prog, cols)
                 res = self._post(prog, cols)
                 if tiers:
                     res.stats["distinct_count_device"] = tiers
@@ -1224,6 +1225,61 @@ class PreparedQuery:
             return None
         return dp.count()
 
+    # ------------------------------------------------------------------ variances
+    def _moments(self, prog: ScanProgram, cols: Dict[str, np.ndarray]) -> None:
+        """``variance`` aggregators: per group the variance of the selected rows' values, a float64
+        column (NaN where the group holds too few rows) that HAVING, ordering and post-aggregations
+        read like a double sum.  On the native GPU engine the moment sums answer
+        (engine/device_exec.py PreparedMoments: exact for long / decimal metrics); everywhere else
+        -- CPU, the reference executor, hashed keys, more than QUANTILE_SELECT_MAX_G groups -- a
+        centred two-pass in float64 over the selected rows does (ops/reference.py group_variances),
+        which is NOT exact."""
+        if not prog.moments:
+            return
+        gid_order = np.asarray(cols["__gid__"], dtype=np.int64)
+        fused = self._moments_fused(prog)
+        if fused is not None:
+            for (name, _, _), res in zip(prog.moments, fused):
+                ok = (gid_order >= 0) & (gid_order < len(res))
+                cols[name] = np.where(ok, res[np.clip(gid_order, 0, max(0, len(res) - 1))], np.nan)
+            return
+        from ..ops.reference import _rows, compute_keys, eval_bexpr, group_variances
+        from .lower import column_tensor
+
+        ds = self.ds
+        rows = _rows(prog) if not prog.empty else torch.zeros(0, dtype=torch.int64, device=ds.device)
+        if rows.numel():
+            rows = rows[eval_bexpr(prog, prog.bexpr, rows)]
+        keys = compute_keys(prog, rows)
+        for name, col, ddof in prog.moments:
+            m = ds.metrics[col]
+            v = column_tensor(ds, col)[rows].to(torch.float64)
+            if m.kind == "decimal" and m.scale:
+                v = v / (10.0 ** int(m.scale))
+            gids, var = group_variances(keys, v, ddof)
+            gids, var = gids.cpu().numpy(), var.cpu().numpy()
+            at = np.clip(np.searchsorted(gids, gid_order), 0, max(0, len(gids) - 1))
+            cols[name] = np.where(gids[at] == gid_order, var[at], np.nan) if len(gids) else \
+                np.full(len(gid_order), np.nan)
+
+    def _moments_fused(self, prog: ScanProgram) -> Optional[list]:
+        """Per variance aggregator its values [G] from the device moment sums, or None where they do
+        not apply (CPU, hashed or ineligible keys, too many groups, an empty shard)."""
+        if prog.empty or self.ds.device.type != "cuda" or not self.engine.use_native:
+            return None
+        mp = self.__dict__.get("_moments_prep")
+        if mp is None:
+            try:
+                from .device_exec import PreparedMoments
+
+                mp = PreparedMoments(prog, prog.moments, QUANTILE_SELECT_MAX_G)
+            except RuntimeError:
+                mp = False
+            self._moments_prep = mp
+        if mp is False:
+            return None
+        return mp.variances()
+
     # ------------------------------------------------------------------ post processing
     def _post(self, prog: ScanProgram, cols: Dict[str, np.ndarray]) -> QueryResult:
         qs = self.qs
@@ -1726,6 +1782,8 @@ def eval_postagg(pa, cols: Dict[str, np.ndarray], n: int):
         return np.full(n, float(pa.value))
     if isinstance(pa, S.HyperUniqueCardinalityPostAggregationSpec):
         return np.asarray(cols[pa.fieldName], dtype=np.float64)
+    if isinstance(pa, S.StddevPostAggregationSpec):
+        return np.sqrt(np.asarray(cols[pa.fieldName], dtype=np.float64))
     if isinstance(pa, S.ArithmeticPostAggregationSpec):
         vals = [np.asarray(eval_postagg(f, cols, n), dtype=np.float64) for f in pa.fields]
         out = vals[0].copy()

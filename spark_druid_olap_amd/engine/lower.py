@@ -329,7 +329,7 @@ class KeyComp:
 @dataclass
 class AggOut:
     name: str
-    kind: str                     # count|sum_i|sum_f|sum_fx|min_i|max_i|min_f|max_f|hll|theta|quantile|distinct
+    kind: str                     # count|sum_i|sum_f|sum_fx|min_i|max_i|min_f|max_f|hll|theta|quantile|distinct|moment
     slot: int = -1
     slot2: int = -1               # sum_fx: fraction slot (value = slot + slot2 * 2^-32)
     hll_index: int = -1
@@ -370,6 +370,8 @@ class ScanProgram:
     quantiles: List[Tuple[str, str, Tuple[float, ...], bool]] = field(default_factory=list)
     # exact distinct counts: (name, dimension, the aggregator's own filter or None, its fops span)
     distincts: List[Tuple[str, str, Any, Tuple[int, int]]] = field(default_factory=list)
+    # variances: (name, metric, delta degrees of freedom: 1 sample, 0 population)
+    moments: List[Tuple[str, str, int]] = field(default_factory=list)
     luts: Dict[str, torch.Tensor] = field(default_factory=dict)       # dim -> f64 value per dictionary id
     lut_ptrs: Dict[float, torch.Tensor] = field(default_factory=dict)  # E_LUT operand -> its table
     # grouping keys functionally determined by a packed key: (key, index of determinant in keys,
@@ -388,9 +390,10 @@ class ScanProgram:
     @property
     def needs_rows(self) -> bool:
         """Some aggregator reads the selected rows themselves (theta KMV, order statistics, exact
-        distinct counts), not an accumulator: strategies that keep only accumulators decline, the
-        executor answers it after the scan (engine/executor.py _theta / _quantile / _distinct)."""
-        return bool(self.thetas or self.quantiles or self.distincts)
+        distinct counts, variances), not an accumulator: strategies that keep only accumulators
+        decline, the executor answers it after the scan (engine/executor.py _theta / _quantile /
+        _distinct / _moments)."""
+        return bool(self.thetas or self.quantiles or self.distincts or self.moments)
 
     @property
     def nhll_total(self) -> int:
@@ -1357,6 +1360,28 @@ class Lowerer:
                 raise LoweringError(f"distinctCount over {a.fieldName!r}: not a dimension")
             prog.distincts.append((a.name, a.fieldName, filt, (0, 0)))
             prog.aggs.append(AggOut(a.name, "distinct", out_type="long", combine="distinct"))
+            return
+        if isinstance(a, S.VarianceAggregationSpec):
+            if self.world is not None and self.world.distributed:
+                # (every rank would answer for its own shard: the integer states are additive, but
+                # they are not reduced across ranks yet -- the SQL layer answers on the host there)
+                raise LoweringError("variance aggregators are not answered across ranks")
+            m = ds.metrics.get(a.fieldName)
+            if m is None:
+                raise LoweringError(f"variance over {a.fieldName!r}: not a metric")
+            if m.sketch is not None or m.kind not in ("long", "double", "decimal"):
+                raise LoweringError(f"variance over the sketch metric {a.fieldName!r}")
+            if a.estimator not in ("sample", "population"):
+                raise LoweringError(f"variance: unknown estimator {a.estimator!r}")
+            if filt is not None:
+                raise LoweringError("variance inside a filtered aggregator is not supported")
+            if self.deterministic and m.kind == "double":
+                # (two passes of f64 atomic adds: a few ulp between runs.  Long / decimal metrics add
+                # integers only and stay bitwise reproducible)
+                raise LoweringError(f"variance over the double metric {a.fieldName!r} is not bitwise reproducible "
+                                    "(deterministic mode)")
+            prog.moments.append((a.name, a.fieldName, 1 if a.estimator == "sample" else 0))
+            prog.aggs.append(AggOut(a.name, "moment", out_type="double", combine="moment"))
             return
         raise LoweringError(f"unsupported aggregator {type(a).__name__}")
 

@@ -258,7 +258,7 @@ def _agg_outputs_dev(prog, acc: torch.Tensor, skip) -> Dict[str, torch.Tensor]:
     """Final aggregator columns on the device (same values as finalize's host conversions)."""
     out = {}
     for a in prog.aggs:
-        if a.name in skip or a.slot < 0 or a.kind in ("hll", "theta", "quantile", "distinct"):
+        if a.name in skip or a.slot < 0 or a.kind in ("hll", "theta", "quantile", "distinct", "moment"):
             continue
         col = acc[:, a.slot]
         if a.kind == "count":
@@ -376,7 +376,7 @@ def _native_sparse(prog, parts: Partials, out_types, want_gid: bool):
         order.append(("dag", j))
     derived_names = {a.name for a, _, _ in getattr(prog, "derived_aggs", ())}
     for a in prog.aggs:
-        if a.name in derived_names or a.slot < 0 or a.kind in ("hll", "theta", "quantile", "distinct"):
+        if a.name in derived_names or a.slot < 0 or a.kind in ("hll", "theta", "quantile", "distinct", "moment"):
             continue
         if a.kind == "count":
             sp = (1, 2, 0, a.slot, 1, 1, 0, 0, 0, 0.0)
@@ -716,7 +716,7 @@ def finalize(prog, parts: Partials, out_types: Optional[Dict[str, str]] = None,
                 cols[a.name] = est_host[a.hll_index]
             else:
                 cols[a.name] = hll_estimates(hll_d[a.hll_index], prog.hll_p) if R else np.zeros(0)
-        elif a.kind in ("theta", "quantile", "distinct"):
+        elif a.kind in ("theta", "quantile", "distinct", "moment"):
             pass  # filled by the executor
     # group count of the result (only its length is read downstream)
     cols["__rows__"] = acc_cols[0] if 0 in acc_cols else np.zeros(R, dtype=np.int8)

@@ -24,6 +24,7 @@
 #include "quantile.h"
 #include "dict_match.h"
 #include "distinct.h"
+#include "moments.h"
 
 namespace sdo {
 template <int U>
@@ -117,6 +118,25 @@ __global__ void dcount_global_regions_kernel(const uint32_t* recs, int rw, int v
 template <bool WAVE_ROW>
 __global__ void dcount_count_kernel(const uint32_t* __restrict__ state, uint32_t G, uint32_t Wg, int64_t null_id,
                                     int64_t* __restrict__ out);
+// moments.hip (shapes: moments.h)
+template <int MODE>
+__global__ void mom_few_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff,
+                                       const uint32_t* __restrict__ seg_lo, const uint32_t* __restrict__ seg_hi,
+                                       int64_t nseg, uint32_t G, const double* __restrict__ mean,
+                                       uint64_t* __restrict__ state);
+template <int MODE>
+__global__ void mom_lds_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff,
+                                       const uint32_t* __restrict__ seg_lo, const uint32_t* __restrict__ seg_hi,
+                                       int64_t nseg, uint32_t g0, uint32_t GL, const double* __restrict__ mean,
+                                       uint64_t* __restrict__ state);
+template <int MODE>
+__global__ void mom_global_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff,
+                                          const uint32_t* __restrict__ seg_lo, const uint32_t* __restrict__ seg_hi,
+                                          int64_t nseg, uint32_t G, const double* __restrict__ mean,
+                                          uint64_t* __restrict__ state);
+__global__ void mom_mean_kernel(const uint64_t* sum, int G, double* mean);
+__global__ void mom_final_kernel(const uint64_t* a, const uint64_t* b, int G, int mode, int ddof, double div,
+                                 double* out);
 // p2p.hip (P2PArgs: p2p.h)
 __global__ void p2p_merge_kernel(P2PArgs a);
 }  // namespace sdo
@@ -1011,6 +1031,88 @@ static void dcount(uint64_t recs, int rw, int voff, uint64_t seg_lo, uint64_t se
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-group moments over a quantile producer's chunk-region records (moments.hip; the arguments of
+// qsel_stats): one accumulation pass of `mode` (moments.h MomMode) into the cleared [G][W] u64
+// `state`.  `tier` -1 picks the tier from G (moments.h mom_tier); 0..2 asks for one that holds G.
+// MOM_F64_DEV reads the group means (`mean`, [G] f64: moments_mean).  Returns the tier used.
+template <int MODE>
+static void mom_launch(int tier, unsigned grid, hipStream_t s, const uint32_t* recs, int rw, int voff,
+                       const uint32_t* seg_lo, const uint32_t* seg_hi, int64_t nseg, uint32_t G, const double* mean,
+                       uint64_t* state) {
+  if (tier == sdo::MOM_TIER_FEW) {
+    hipLaunchKernelGGL(sdo::mom_few_regions_kernel<MODE>, dim3(grid), dim3(256), 0, s, recs, rw, voff, seg_lo, seg_hi,
+                       nseg, G, mean, state);
+  } else if (tier == sdo::MOM_TIER_LDS) {
+    // one pass per key slice of (nearly) equal size, each table within the LDS budget
+    const uint32_t cap = (uint32_t)sdo::mom_lds_groups(MODE);
+    const uint32_t slices = (G + cap - 1) / cap, GL = (G + slices - 1) / slices;
+    const size_t per = 8 * (sdo::mom_words(MODE) - (sdo::mom_counts(MODE) ? 1 : 0)) + (sdo::mom_counts(MODE) ? 4 : 0);
+    for (uint32_t g0 = 0; g0 < G; g0 += GL) {
+      const uint32_t n = std::min(GL, G - g0);
+      hipLaunchKernelGGL(sdo::mom_lds_regions_kernel<MODE>, dim3(grid), dim3(256), n * per, s, recs, rw, voff, seg_lo,
+                         seg_hi, nseg, g0, n, mean, state);
+    }
+  } else {
+    hipLaunchKernelGGL(sdo::mom_global_regions_kernel<MODE>, dim3(grid), dim3(256), 0, s, recs, rw, voff, seg_lo,
+                       seg_hi, nseg, G, mean, state);
+  }
+}
+
+static int moments_accum(uint64_t recs, int rw, int voff, uint64_t seg_lo, uint64_t seg_hi, int64_t nseg, int64_t G,
+                         int mode, int tier, uint64_t mean, uint64_t state, uint64_t stream) {
+  qsel_check(rw, voff, G);
+  if (mode < sdo::MOM_INT2 || mode > sdo::MOM_F64_DEV) throw std::invalid_argument("moments_accum: mode");
+  if (nseg < 0 || !state || (mode == sdo::MOM_F64_DEV && !mean)) throw std::invalid_argument("moments_accum: arguments");
+  const int fit = sdo::mom_tier(mode, G);
+  if (tier < 0) tier = fit;
+  if (tier > sdo::MOM_TIER_GLOBAL || tier < fit) throw std::invalid_argument("moments_accum: tier does not hold G");
+  const int W = sdo::mom_words(mode);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(sdo::qsel_clear_kernel, dim3(grid_for(G * W * 2, 256, 4096)), dim3(256), 0, s, (uint32_t*)state,
+                     G * W * 2);
+  check(hipGetLastError(), "moments clear launch");
+  if (nseg == 0) return tier;
+  // few / lds: every workgroup ends with a flush of its table onto the same global words, so fewer,
+  // longer-running workgroups (the bound the quantile histograms use); global: one per region
+  const unsigned grid = (unsigned)std::min<int64_t>(nseg, tier == sdo::MOM_TIER_GLOBAL ? 4096 : 1024);
+  const uint32_t* r = (const uint32_t*)recs;
+  const uint32_t *lo = (const uint32_t*)seg_lo, *hi = (const uint32_t*)seg_hi;
+  const double* mu = (const double*)mean;
+  uint64_t* st = (uint64_t*)state;
+  switch (mode) {
+    case sdo::MOM_INT2: mom_launch<sdo::MOM_INT2>(tier, grid, s, r, rw, voff, lo, hi, nseg, (uint32_t)G, mu, st); break;
+    case sdo::MOM_INT4: mom_launch<sdo::MOM_INT4>(tier, grid, s, r, rw, voff, lo, hi, nseg, (uint32_t)G, mu, st); break;
+    case sdo::MOM_F64_SUM: mom_launch<sdo::MOM_F64_SUM>(tier, grid, s, r, rw, voff, lo, hi, nseg, (uint32_t)G, mu, st); break;
+    default: mom_launch<sdo::MOM_F64_DEV>(tier, grid, s, r, rw, voff, lo, hi, nseg, (uint32_t)G, mu, st); break;
+  }
+  check(hipGetLastError(), "moments accumulation launch");
+  return tier;
+}
+
+// mean[g] = sum x / n from a MOM_F64_SUM state (0 for an empty group)
+static void moments_mean(uint64_t sum, int64_t G, uint64_t mean, uint64_t stream) {
+  if (G <= 0 || G > (1 << 20) || !sum || !mean) throw std::invalid_argument("moments_mean: arguments");
+  hipLaunchKernelGGL(sdo::mom_mean_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const uint64_t*)sum, (int)G, (double*)mean);
+  check(hipGetLastError(), "mom_mean_kernel launch");
+}
+
+// out[g] (f64) = the variance with `ddof` delta degrees of freedom, NaN where n <= ddof.  Integer
+// modes: `a` the accumulated state, divided by `div` (10^(2 scale) of a decimal); MOM_F64_DEV: `a`
+// the MOM_F64_SUM state (the counts), `b` the MOM_F64_DEV state.
+static void moments_final(uint64_t a, uint64_t b, int64_t G, int mode, int ddof, double div, uint64_t out,
+                          uint64_t stream) {
+  if (G <= 0 || G > (1 << 20) || !a || !out) throw std::invalid_argument("moments_final: arguments");
+  if (mode != sdo::MOM_INT2 && mode != sdo::MOM_INT4 && mode != sdo::MOM_F64_DEV)
+    throw std::invalid_argument("moments_final: mode");
+  if ((mode == sdo::MOM_F64_DEV && !b) || ddof < 0 || ddof > 1 || !(div >= 1.0))
+    throw std::invalid_argument("moments_final: arguments");
+  hipLaunchKernelGGL(sdo::mom_final_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const uint64_t*)a, (const uint64_t*)b, (int)G, mode, ddof, div, (double*)out);
+  check(hipGetLastError(), "mom_final_kernel launch");
+}
+
+// ---------------------------------------------------------------------------------------------
 // LIKE / contains / fragment over a dictionary's device text heap (dict_match.hip): bit e of `out`
 // says entry e matches `program` (a packed DmProgram); when the program folds case, bit e of
 // `nonascii` says entry e holds a byte >= 0x80 (the host re-evaluates those).  `heap` is 16-byte
@@ -1311,6 +1413,9 @@ PYBIND11_MODULE(_sdo_native, m) {
   m.def("qsel_stats", &qsel_stats);
   m.def("qsel_select", &qsel_select);
   m.def("dcount", &dcount);
+  m.def("moments_accum", &moments_accum);
+  m.def("moments_mean", &moments_mean);
+  m.def("moments_final", &moments_final);
   m.def("dict_match", &dict_match);
   m.def("dict_match_layout", &dict_match_layout);
   m.def("part_agg", &part_agg);

@@ -412,6 +412,25 @@ def distinct_counts(keys: torch.Tensor, ids: torch.Tensor, D: int, null_id: int 
     return torch.unique_consecutive(torch.div(pairs, int(D), rounding_mode="floor"), return_counts=True)
 
 
+def group_variances(keys: torch.Tensor, v: torch.Tensor, ddof: int):
+    """Variance by group in float64, centred two-pass: (group keys ascending, variance per group, NaN
+    where the group holds <= ``ddof`` rows) of the (group key, value) pairs.  NOT exact: values
+    beyond 2^53 are rounded on entry and the sums round as they go (relative error about
+    n 2^-53) -- the engine's answer wherever ops/csrc/moments.hip does not apply."""
+    gids, inv, cnt = torch.unique(keys.to(torch.int64), return_inverse=True, return_counts=True)
+    v = v.to(torch.float64)
+    n = cnt.to(torch.float64)
+
+    def by_group(x):
+        return torch.zeros(len(gids), dtype=torch.float64, device=v.device).index_add_(0, inv, x)
+
+    d = v - (by_group(v) / n)[inv]
+    sd = by_group(d)
+    m2 = torch.clamp(by_group(d * d) - sd * sd / n, min=0.0)
+    nan = torch.full_like(n, float("nan"))
+    return gids, torch.where(n > ddof, m2 / torch.clamp(n - ddof, min=1.0), nan)
+
+
 def run_reference_mask(prog) -> torch.Tensor:
     """Row ids passing the filter (select queries)."""
     dev = prog.ds.device

@@ -525,6 +525,19 @@ class DistinctCountAggregationSpec(Spec, _Decodable):
     type: str = "distinctCount"
 
 
+@_register("aggregation", "variance")
+@dataclass
+class VarianceAggregationSpec(Spec, _Decodable):
+    """Variance of a long / decimal / double metric over the selected rows (the ``variance``
+    aggregator of Druid's stats extension).  ``estimator``: ``"sample"`` (n - 1 in the denominator,
+    the default) or ``"population"`` (n).  The result is a double, NaN for a group of fewer than two
+    rows (one row, under ``"population"``: 0)."""
+    name: str
+    fieldName: str
+    estimator: str = "sample"
+    type: str = "variance"
+
+
 # ============================================================================ post aggregations
 @_register("postagg", "fieldAccess")
 @dataclass
@@ -548,6 +561,15 @@ class HyperUniqueCardinalityPostAggregationSpec(Spec, _Decodable):
     fieldName: str
     name: Optional[str] = None
     type: str = "hyperUniqueCardinality"
+
+
+@_register("postagg", "stddev")
+@dataclass
+class StddevPostAggregationSpec(Spec, _Decodable):
+    """Square root of the named ``variance`` aggregator's column (the stats extension's ``stddev``)."""
+    name: str
+    fieldName: str
+    type: str = "stddev"
 
 
 @_register("postagg", "arithmetic")

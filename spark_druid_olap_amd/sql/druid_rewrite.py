@@ -693,12 +693,12 @@ class DruidRewriter:
             prefs = []
             for part in parts:
                 spec_, t = part[0], part[1]
-                if id(spec_) in shared:  # (a quantiles aggregator several calls read)
+                if id(spec_) in shared:  # (a quantiles / variance aggregator several calls read)
                     prefs.append(shared[id(spec_)])
                     continue
                 aggs.append(spec_)
                 r = A.Ref(A.new_id(), spec_.name, t)
-                if isinstance(spec_, S.QuantilesAggregationSpec):
+                if isinstance(spec_, (S.QuantilesAggregationSpec, S.VarianceAggregationSpec)):
                     shared[id(spec_)] = r
                 drefs.append(r)
                 columns.append((spec_.name, t, part[2] if len(part) > 2 else "value"))
@@ -952,7 +952,39 @@ class DruidRewriter:
             return [(spec_, t)], lambda rs: rs[0]
         if n in A.QUANTILE_FUNCS:
             return self._quantile_agg(pf, call, names, rolled)
+        if n in VARIANCE_FUNCS:
+            return self._variance_agg(pf, call, names, rolled)
         raise NotPushable(f"aggregate {n} is not pushable")
+
+    def _variance_agg(self, pf: PF, call: A.Call, names: "_Names", rolled: bool):
+        """stddev / stddev_samp / stddev_pop / variance / var_samp / var_pop over a plain long /
+        decimal / double metric -> ONE ``variance`` aggregator per (column, estimator) of the query;
+        the stddev family projects its square root.  A group of too few rows holds NaN, which the
+        result conversion turns into NULL as the host plan's pandas NaN.  The moment sums are
+        per shard: a distributed session answers on the host."""
+        n = call.name
+        sqrt, estimator = VARIANCE_FUNCS[n]
+        if call.distinct:
+            raise NotPushable(f"{n}(DISTINCT)")
+        if rolled or getattr(pf.table.info.datasource, "rollup", False):
+            raise NotPushable(f"{n} over a rolled-up datasource")
+        if self.session.engine.world.distributed:
+            raise NotPushable(f"{n} across ranks")
+        x = call.args[0] if len(call.args) == 1 else None
+        if not isinstance(x, A.Ref):
+            raise NotPushable(f"{n} over an expression")
+        c = self._column(pf, x)
+        m = pf.table.info.datasource.metrics.get(c.druid_column) if c.is_metric else None
+        if m is None or m.sketch is not None or m.kind not in ("long", "decimal", "double"):
+            raise NotPushable(f"{n} over {c.column}: not a long / decimal / double metric")
+        if m.kind == "double" and (self.session.engine.deterministic or
+                                   bool(self.conf.typed("spark.sparklinedata.druid.deterministic"))):
+            raise NotPushable(f"{n} over the double metric {c.column} in deterministic mode")
+        spec = names.variances.get((c.druid_column, estimator))
+        if spec is None:
+            spec = names.variances[(c.druid_column, estimator)] = \
+                S.VarianceAggregationSpec(names.agg(), c.druid_column, estimator)
+        return [(spec, "double")], (lambda rs: A.Call("sqrt", (rs[0],))) if sqrt else (lambda rs: rs[0])
 
     def _quantile_agg(self, pf: PF, call: A.Call, names: "_Names", rolled: bool):
         """percentile / median / percentile_approx over a plain metric (long, decimal, double) or a
@@ -1473,11 +1505,17 @@ def _non_null_dim(q, out_name: str, ds) -> bool:
     return False
 
 
+# SQL variance family -> (project the square root, the variance aggregator's estimator)
+VARIANCE_FUNCS = {"stddev": (True, "sample"), "stddev_samp": (True, "sample"), "stddev_pop": (True, "population"),
+                  "variance": (False, "sample"), "var_samp": (False, "sample"), "var_pop": (False, "population")}
+
+
 class _Names:
     def __init__(self):
         self.n = 0
         self.used: Set[str] = set()
         self.quantiles: Dict[tuple, object] = {}  # (column, interpolate) -> its one quantiles aggregator
+        self.variances: Dict[tuple, object] = {}  # (column, estimator) -> its one variance aggregator
 
     def agg(self) -> str:
         self.n += 1
