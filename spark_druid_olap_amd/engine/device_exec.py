@@ -1486,6 +1486,7 @@ class PreparedEmit:
         ep.aops = [{"kind": D.A_ROWID, "col": -1, "expr": None, "filter": None, "slot": 0, "hll": -1}]
         ep.slots = [(D.S_SUM_I, 0)]
         ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
+        ep.comoments = []
         ep.presence_only = False
         self.prog = ep
         self.dev = prog.ds.device
@@ -1557,6 +1558,7 @@ def theta_producer_prog(prog: ScanProgram, cols: List[str]) -> ScanProgram:
                for i, c in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(cols)
     ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
+    ep.comoments = []
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("theta: program not eligible")
@@ -1743,6 +1745,7 @@ def quantile_producer_prog(prog: ScanProgram, cols: List[str]) -> ScanProgram:
                for i, c in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(cols)
     ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
+    ep.comoments = []
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("quantile: program not eligible")
@@ -1949,6 +1952,84 @@ class PreparedMoments(_QvalRecords):
             PART_POOL.release(slab)
 
 
+CO_INT2, CO_INT4, CO_F64_SUM, CO_F64_DEV = range(4)  # ops/csrc/comoments.h CoMode
+CO_COVAR, CO_CORR = range(2)                         # ... and CoKind (the tiers are MOM_TIERS)
+
+
+def co_words(mode: int, sq: bool) -> int:
+    """Words of a pair's state (ops/csrc/comoments.h co_words)."""
+    if mode == CO_F64_SUM:
+        return 3
+    if mode == CO_F64_DEV:
+        return 5 if sq else 3
+    return 3 + (2 if mode == CO_INT2 else 4) * (3 if sq else 1)
+
+
+class PreparedComoments(_QvalRecords):
+    """``covariance`` / ``correlation`` aggregators pushed into the scan: the quantile producer's
+    records over the union of the pairs' columns (one pass), then per distinct UNORDERED pair the
+    co-moment sums of ops/csrc/comoments.hip -- (y, x) is the pair (x, y), and corr / covar_samp /
+    covar_pop of a pair share its state, which holds the squares only when a correlation asks --
+    and per aggregator the finalise kernel.  Long / decimal pairs: ONE exact pass, bitwise
+    reproducible (two-digit products when both stored types are at most 32 bits wide, else four).
+    A pair with a double column: a sum pass, the means, a pass over the deviations.  Nothing is read
+    back before the result copy.  G <= ``max_g``."""
+
+    def __init__(self, prog: ScanProgram, comoments: list, max_g: int):
+        super().__init__(prog, sorted({c for _, x, y, _ in comoments for c in (x, y)}), max_g, "comoments")
+        ds = prog.ds
+        # per unordered pair: (value offsets, mode, with squares, double-column bits, decimal scales)
+        self.passes = {}
+        for _, x, y, kind in comoments:
+            pair = tuple(sorted((x, y)))
+            mx, my = (ds.metrics[c] for c in pair)
+            dbl = (1 if mx.kind == "double" else 0) | (2 if my.kind == "double" else 0)
+            if dbl:
+                mode = CO_F64_SUM
+            else:
+                mode = CO_INT2 if max(mx.data.dtype.itemsize, my.data.dtype.itemsize) <= 4 else CO_INT4
+            sq = kind == "corr" or (pair in self.passes and self.passes[pair][2])
+            scale = sum(int(m.scale) for m in (mx, my) if m.kind == "decimal")
+            self.passes[pair] = (tuple(self.voff(c) for c in pair), mode, sq, dbl, scale)
+        self.sel = [(tuple(sorted((x, y))), kind) for _, x, y, kind in comoments]
+        self.tiers = []  # (per distinct pair of the last run: the tier its first pass took)
+
+    def values(self) -> list:
+        """Per aggregator its covariances / correlations [G] (host float64; NaN where undefined)."""
+        nat, st = native.load(), native._stream(self.dev)
+        dev, G = self.dev, self.G
+        pend = torch.empty(max(1, self.nch), dtype=torch.int32, device=dev)
+        slab = PART_POOL.acquire(dev, self.words)
+        try:
+            regions = self.produce(nat, st, slab, pend)
+            recs = slab.recs1.data_ptr()
+            states, self.tiers = {}, []
+            for pair, ((vx, vy), mode, sq, dbl, _) in self.passes.items():
+                a = torch.empty(G * co_words(mode, sq), dtype=torch.int64, device=dev)
+                tier = nat.comoments_accum(recs, self.rw, vx, vy, *regions, mode, sq, dbl, -1, 0, a.data_ptr(), st)
+                b = None
+                if mode == CO_F64_SUM:
+                    mean = torch.empty(G * 2, dtype=torch.float64, device=dev)
+                    b = torch.empty(G * co_words(CO_F64_DEV, sq), dtype=torch.int64, device=dev)
+                    nat.comoments_mean(a.data_ptr(), G, mean.data_ptr(), st)
+                    nat.comoments_accum(recs, self.rw, vx, vy, *regions, CO_F64_DEV, sq, dbl, -1, mean.data_ptr(),
+                                        b.data_ptr(), st)
+                states[pair] = (a, b)
+                self.tiers.append(MOM_TIERS[tier])
+            res = []
+            for pair, kind in self.sel:
+                _, mode, sq, _, scale = self.passes[pair]
+                a, b = states[pair]
+                out = torch.empty(G, dtype=torch.float64, device=dev)
+                nat.comoments_final(a.data_ptr(), b.data_ptr() if b is not None else 0, G,
+                                    CO_F64_DEV if b is not None else mode, sq, CO_CORR if kind == "corr" else CO_COVAR,
+                                    1 if kind == "cov-samp" else 0, float(10 ** scale), out.data_ptr(), st)
+                res.append(out)
+            return [r.cpu().numpy() for r in res]
+        finally:
+            PART_POOL.release(slab)
+
+
 def distinct_producer_prog(prog: ScanProgram, cols: list) -> ScanProgram:
     """The scan program of a distinct producer: ``prog``'s filter, ranges and group key, one
     A_DISTINCT aggregator (the dimension's dictionary id, one record word) per (column, aggregator
@@ -1963,6 +2044,7 @@ def distinct_producer_prog(prog: ScanProgram, cols: list) -> ScanProgram:
                 "filt_off": off, "filt_len": n} for i, (c, (off, n)) in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(cols)
     ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
+    ep.comoments = []
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("distinct: program not eligible")

@@ -500,9 +500,12 @@ class PreparedQuery:
                 self._quantile(self._full_prog, cols)
                 tiers = self._distinct(self._full_prog, cols)
                 self._moments(self._full_prog, cols)
+                co_tiers = self._comoments(self._full_prog, cols)
                 res = self._post(prog, cols)
                 if tiers:
                     res.stats["distinct_count_device"] = tiers
+                if co_tiers:
+                    res.stats["comoments_device"] = co_tiers
             t4 = time.perf_counter()
             res.stats.update(scan_ms=(t1 - t0) * 1e3, merge_ms=(t2 - t1) * 1e3, finalize_ms=(t3 - t2) * 1e3,
                              post_ms=(t4 - t3) * 1e3)
@@ -1279,6 +1282,66 @@ class PreparedQuery:
         if mp is False:
             return None
         return mp.variances()
+
+    # ------------------------------------------------------------------ covariances / correlations
+    def _comoments(self, prog: ScanProgram, cols: Dict[str, np.ndarray]) -> Optional[list]:
+        """``covariance`` / ``correlation`` aggregators: per group the statistic of the selected
+        rows' value pairs, a float64 column (NaN where undefined) that HAVING, ordering and
+        post-aggregations read like a double sum.  On the native GPU engine the co-moment sums
+        answer (engine/device_exec.py PreparedComoments: exact for long / decimal pairs); everywhere
+        else -- CPU, the reference executor, hashed keys, more than QUANTILE_SELECT_MAX_G groups --
+        a centred two-pass in float64 does (ops/reference.py group_comoments), which is NOT exact.
+        Returns the tier per pair when the device sums answered (the result's ``comoments_device``
+        stats entry: without it the answer is the float64 one), else None."""
+        if not prog.comoments:
+            return None
+        gid_order = np.asarray(cols["__gid__"], dtype=np.int64)
+        fused = self._comoments_fused(prog)
+        if fused is not None:
+            for (name, _, _, _), res in zip(prog.comoments, fused):
+                ok = (gid_order >= 0) & (gid_order < len(res))
+                cols[name] = np.where(ok, res[np.clip(gid_order, 0, max(0, len(res) - 1))], np.nan)
+            return list(self._comoments_prep.tiers)
+        from ..ops.reference import _rows, compute_keys, eval_bexpr, group_comoments
+        from .lower import column_tensor
+
+        ds = self.ds
+        rows = _rows(prog) if not prog.empty else torch.zeros(0, dtype=torch.int64, device=ds.device)
+        if rows.numel():
+            rows = rows[eval_bexpr(prog, prog.bexpr, rows)]
+        keys = compute_keys(prog, rows)
+
+        def values(col):
+            m = ds.metrics[col]
+            v = column_tensor(ds, col)[rows].to(torch.float64)
+            return v / (10.0 ** int(m.scale)) if m.kind == "decimal" and m.scale else v
+
+        for name, cx, cy, kind in prog.comoments:
+            gids, val = group_comoments(keys, values(cx), values(cy), kind)
+            gids, val = gids.cpu().numpy(), val.cpu().numpy()
+            at = np.clip(np.searchsorted(gids, gid_order), 0, max(0, len(gids) - 1))
+            cols[name] = np.where(gids[at] == gid_order, val[at], np.nan) if len(gids) else \
+                np.full(len(gid_order), np.nan)
+        return None
+
+    def _comoments_fused(self, prog: ScanProgram) -> Optional[list]:
+        """Per covariance / correlation aggregator its values [G] from the device co-moment sums, or
+        None where they do not apply (CPU, hashed or ineligible keys, too many groups, an empty
+        shard)."""
+        if prog.empty or self.ds.device.type != "cuda" or not self.engine.use_native:
+            return None
+        cp = self.__dict__.get("_comoments_prep")
+        if cp is None:
+            try:
+                from .device_exec import PreparedComoments
+
+                cp = PreparedComoments(prog, prog.comoments, QUANTILE_SELECT_MAX_G)
+            except RuntimeError:
+                cp = False
+            self._comoments_prep = cp
+        if cp is False:
+            return None
+        return cp.values()
 
     # ------------------------------------------------------------------ post processing
     def _post(self, prog: ScanProgram, cols: Dict[str, np.ndarray]) -> QueryResult:

@@ -372,6 +372,8 @@ class ScanProgram:
     distincts: List[Tuple[str, str, Any, Tuple[int, int]]] = field(default_factory=list)
     # variances: (name, metric, delta degrees of freedom: 1 sample, 0 population)
     moments: List[Tuple[str, str, int]] = field(default_factory=list)
+    # covariances / correlations: (name, metric x, metric y, kind: "cov-pop" | "cov-samp" | "corr")
+    comoments: List[Tuple[str, str, str, str]] = field(default_factory=list)
     luts: Dict[str, torch.Tensor] = field(default_factory=dict)       # dim -> f64 value per dictionary id
     lut_ptrs: Dict[float, torch.Tensor] = field(default_factory=dict)  # E_LUT operand -> its table
     # grouping keys functionally determined by a packed key: (key, index of determinant in keys,
@@ -390,10 +392,10 @@ class ScanProgram:
     @property
     def needs_rows(self) -> bool:
         """Some aggregator reads the selected rows themselves (theta KMV, order statistics, exact
-        distinct counts, variances), not an accumulator: strategies that keep only accumulators
-        decline, the executor answers it after the scan (engine/executor.py _theta / _quantile /
-        _distinct / _moments)."""
-        return bool(self.thetas or self.quantiles or self.distincts or self.moments)
+        distinct counts, variances, covariances), not an accumulator: strategies that keep only
+        accumulators decline, the executor answers it after the scan (engine/executor.py _theta /
+        _quantile / _distinct / _moments / _comoments)."""
+        return bool(self.thetas or self.quantiles or self.distincts or self.moments or self.comoments)
 
     @property
     def nhll_total(self) -> int:
@@ -1381,6 +1383,30 @@ class Lowerer:
                 raise LoweringError(f"variance over the double metric {a.fieldName!r} is not bitwise reproducible "
                                     "(deterministic mode)")
             prog.moments.append((a.name, a.fieldName, 1 if a.estimator == "sample" else 0))
+            prog.aggs.append(AggOut(a.name, "moment", out_type="double", combine="moment"))
+            return
+        if isinstance(a, (S.CovarianceAggregationSpec, S.CorrelationAggregationSpec)):
+            what = "covariance" if isinstance(a, S.CovarianceAggregationSpec) else "correlation"
+            if self.world is not None and self.world.distributed:
+                # (as variance: the integer states are additive but not reduced across ranks yet)
+                raise LoweringError(f"{what} aggregators are not answered across ranks")
+            for f in (a.fieldName, a.fieldName2):
+                m = ds.metrics.get(f)
+                if m is None:
+                    raise LoweringError(f"{what} over {f!r}: not a metric")
+                if m.sketch is not None or m.kind not in ("long", "double", "decimal"):
+                    raise LoweringError(f"{what} over the sketch metric {f!r}")
+            if what == "covariance" and a.estimator not in ("sample", "population"):
+                raise LoweringError(f"covariance: unknown estimator {a.estimator!r}")
+            if filt is not None:
+                raise LoweringError(f"{what} inside a filtered aggregator is not supported")
+            for f in (a.fieldName, a.fieldName2):
+                if self.deterministic and ds.metrics[f].kind == "double":
+                    # (a pair with a double column takes two passes of f64 atomic adds)
+                    raise LoweringError(f"{what} over the double metric {f!r} is not bitwise reproducible "
+                                        "(deterministic mode)")
+            kind = "corr" if what == "correlation" else "cov-samp" if a.estimator == "sample" else "cov-pop"
+            prog.comoments.append((a.name, a.fieldName, a.fieldName2, kind))
             prog.aggs.append(AggOut(a.name, "moment", out_type="double", combine="moment"))
             return
         raise LoweringError(f"unsupported aggregator {type(a).__name__}")

@@ -25,6 +25,7 @@
 #include "dict_match.h"
 #include "distinct.h"
 #include "moments.h"
+#include "comoments.h"
 
 namespace sdo {
 template <int U>
@@ -137,6 +138,25 @@ __global__ void mom_global_regions_kernel(const uint32_t* __restrict__ recs, int
 __global__ void mom_mean_kernel(const uint64_t* sum, int G, double* mean);
 __global__ void mom_final_kernel(const uint64_t* a, const uint64_t* b, int G, int mode, int ddof, double div,
                                  double* out);
+// comoments.hip (shapes: comoments.h)
+template <int MODE, bool SQ>
+__global__ void co_few_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff_x, int voff_y,
+                                      const uint32_t* __restrict__ seg_lo, const uint32_t* __restrict__ seg_hi,
+                                      int64_t nseg, uint32_t G, int dbl, const double* __restrict__ mean,
+                                      uint64_t* __restrict__ state);
+template <int MODE, bool SQ>
+__global__ void co_lds_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff_x, int voff_y,
+                                      const uint32_t* __restrict__ seg_lo, const uint32_t* __restrict__ seg_hi,
+                                      int64_t nseg, uint32_t g0, uint32_t GL, int dbl,
+                                      const double* __restrict__ mean, uint64_t* __restrict__ state);
+template <int MODE, bool SQ>
+__global__ void co_global_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff_x, int voff_y,
+                                         const uint32_t* __restrict__ seg_lo, const uint32_t* __restrict__ seg_hi,
+                                         int64_t nseg, uint32_t G, int dbl, const double* __restrict__ mean,
+                                         uint64_t* __restrict__ state);
+__global__ void co_mean_kernel(const uint64_t* sum, int G, double* mean);
+__global__ void co_final_kernel(const uint64_t* a, const uint64_t* b, int G, int mode, int sq, int kind, int ddof,
+                                double div, double* out);
 // p2p.hip (P2PArgs: p2p.h)
 __global__ void p2p_merge_kernel(P2PArgs a);
 }  // namespace sdo
@@ -1113,6 +1133,100 @@ static void moments_final(uint64_t a, uint64_t b, int64_t G, int mode, int ddof,
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-group co-moments of a column pair over the same records (comoments.hip): one accumulation
+// pass of `mode` (comoments.h CoMode; `sq`: with the squares a correlation needs) over the values
+// at `voff_x` and `voff_y` into the cleared [G][W] u64 `state`.  `dbl` bit 0 / 1: x / y is a double
+// column (the f64 modes).  `tier` -1 picks the tier from G (comoments.h co_tier); 0..2 asks for one
+// that holds G.  CO_F64_DEV reads the pair's means (`mean`, [G][2] f64: comoments_mean).  Returns
+// the tier used.
+template <int MODE, bool SQ>
+static void co_launch(int tier, unsigned grid, hipStream_t s, const uint32_t* recs, int rw, int voff_x, int voff_y,
+                      const uint32_t* seg_lo, const uint32_t* seg_hi, int64_t nseg, uint32_t G, int dbl,
+                      const double* mean, uint64_t* state) {
+  if (tier == sdo::CO_TIER_FEW) {
+    hipLaunchKernelGGL((sdo::co_few_regions_kernel<MODE, SQ>), dim3(grid), dim3(256), 0, s, recs, rw, voff_x, voff_y,
+                       seg_lo, seg_hi, nseg, G, dbl, mean, state);
+  } else if (tier == sdo::CO_TIER_LDS) {
+    // one pass per key slice of (nearly) equal size, each table within the LDS budget
+    const uint32_t cap = (uint32_t)sdo::co_lds_groups(MODE, SQ);
+    const uint32_t slices = (G + cap - 1) / cap, GL = (G + slices - 1) / slices;
+    for (uint32_t g0 = 0; g0 < G; g0 += GL) {
+      const uint32_t n = std::min(GL, G - g0);
+      hipLaunchKernelGGL((sdo::co_lds_regions_kernel<MODE, SQ>), dim3(grid), dim3(256),
+                         n * (size_t)sdo::co_state_bytes(MODE, SQ), s, recs, rw, voff_x, voff_y, seg_lo, seg_hi, nseg,
+                         g0, n, dbl, mean, state);
+    }
+  } else {
+    hipLaunchKernelGGL((sdo::co_global_regions_kernel<MODE, SQ>), dim3(grid), dim3(256), 0, s, recs, rw, voff_x,
+                       voff_y, seg_lo, seg_hi, nseg, G, dbl, mean, state);
+  }
+}
+
+static int comoments_accum(uint64_t recs, int rw, int voff_x, int voff_y, uint64_t seg_lo, uint64_t seg_hi,
+                           int64_t nseg, int64_t G, int mode, bool sq, int dbl, int tier, uint64_t mean,
+                           uint64_t state, uint64_t stream) {
+  qsel_check(rw, voff_x, G);
+  qsel_check(rw, voff_y, G);
+  if (mode < sdo::CO_INT2 || mode > sdo::CO_F64_DEV) throw std::invalid_argument("comoments_accum: mode");
+  const bool f64 = mode == sdo::CO_F64_SUM || mode == sdo::CO_F64_DEV;
+  if (nseg < 0 || !state || (mode == sdo::CO_F64_DEV && !mean) || dbl < 0 || dbl > 3 || f64 != (dbl != 0))
+    throw std::invalid_argument("comoments_accum: arguments");
+  if (mode == sdo::CO_F64_SUM) sq = false;  // (the first pass keeps no squares)
+  const int fit = sdo::co_tier(mode, sq, G);
+  if (tier < 0) tier = fit;
+  if (tier > sdo::CO_TIER_GLOBAL || tier < fit) throw std::invalid_argument("comoments_accum: tier does not hold G");
+  const int W = sdo::co_words(mode, sq);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(sdo::qsel_clear_kernel, dim3(grid_for(G * W * 2, 256, 4096)), dim3(256), 0, s, (uint32_t*)state,
+                     G * W * 2);
+  check(hipGetLastError(), "comoments clear launch");
+  if (nseg == 0) return tier;
+  // (the grids of moments_accum: few / lds workgroups end with a flush onto the same global words)
+  const unsigned grid = (unsigned)std::min<int64_t>(nseg, tier == sdo::CO_TIER_GLOBAL ? 4096 : 1024);
+  const uint32_t* r = (const uint32_t*)recs;
+  const uint32_t *lo = (const uint32_t*)seg_lo, *hi = (const uint32_t*)seg_hi;
+  const double* mu = (const double*)mean;
+  uint64_t* st = (uint64_t*)state;
+#define SDO_CO_CASE(M, Q) \
+  co_launch<sdo::M, Q>(tier, grid, s, r, rw, voff_x, voff_y, lo, hi, nseg, (uint32_t)G, dbl, mu, st)
+  switch (mode) {
+    case sdo::CO_INT2: sq ? SDO_CO_CASE(CO_INT2, true) : SDO_CO_CASE(CO_INT2, false); break;
+    case sdo::CO_INT4: sq ? SDO_CO_CASE(CO_INT4, true) : SDO_CO_CASE(CO_INT4, false); break;
+    case sdo::CO_F64_SUM: SDO_CO_CASE(CO_F64_SUM, false); break;
+    default: sq ? SDO_CO_CASE(CO_F64_DEV, true) : SDO_CO_CASE(CO_F64_DEV, false); break;
+  }
+#undef SDO_CO_CASE
+  check(hipGetLastError(), "comoments accumulation launch");
+  return tier;
+}
+
+// mean[g] = (sum x / n, sum y / n) from a CO_F64_SUM state (0 for an empty group)
+static void comoments_mean(uint64_t sum, int64_t G, uint64_t mean, uint64_t stream) {
+  if (G <= 0 || G > (1 << 20) || !sum || !mean) throw std::invalid_argument("comoments_mean: arguments");
+  hipLaunchKernelGGL(sdo::co_mean_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const uint64_t*)sum, (int)G, (double*)mean);
+  check(hipGetLastError(), "co_mean_kernel launch");
+}
+
+// out[g] (f64): `kind` CO_COVAR, the covariance with `ddof` delta degrees of freedom divided by `div`
+// (10^(scale x + scale y) of decimals), NaN where n <= ddof; CO_CORR, the correlation in [-1, 1], NaN
+// where n < 2 or a column is constant in the group (the state must hold the squares: `sq`).  Integer
+// modes: `a` the accumulated state; CO_F64_DEV: `a` the CO_F64_SUM state (the counts), `b` the
+// CO_F64_DEV state.
+static void comoments_final(uint64_t a, uint64_t b, int64_t G, int mode, bool sq, int kind, int ddof, double div,
+                            uint64_t out, uint64_t stream) {
+  if (G <= 0 || G > (1 << 20) || !a || !out) throw std::invalid_argument("comoments_final: arguments");
+  if (mode != sdo::CO_INT2 && mode != sdo::CO_INT4 && mode != sdo::CO_F64_DEV)
+    throw std::invalid_argument("comoments_final: mode");
+  if (kind != sdo::CO_COVAR && kind != sdo::CO_CORR) throw std::invalid_argument("comoments_final: kind");
+  if ((mode == sdo::CO_F64_DEV && !b) || (kind == sdo::CO_CORR && !sq) || ddof < 0 || ddof > 1 || !(div >= 1.0))
+    throw std::invalid_argument("comoments_final: arguments");
+  hipLaunchKernelGGL(sdo::co_final_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const uint64_t*)a, (const uint64_t*)b, (int)G, mode, sq ? 1 : 0, kind, ddof, div, (double*)out);
+  check(hipGetLastError(), "co_final_kernel launch");
+}
+
+// ---------------------------------------------------------------------------------------------
 // LIKE / contains / fragment over a dictionary's device text heap (dict_match.hip): bit e of `out`
 // says entry e matches `program` (a packed DmProgram); when the program folds case, bit e of
 // `nonascii` says entry e holds a byte >= 0x80 (the host re-evaluates those).  `heap` is 16-byte
@@ -1416,6 +1530,9 @@ PYBIND11_MODULE(_sdo_native, m) {
   m.def("moments_accum", &moments_accum);
   m.def("moments_mean", &moments_mean);
   m.def("moments_final", &moments_final);
+  m.def("comoments_accum", &comoments_accum);
+  m.def("comoments_mean", &comoments_mean);
+  m.def("comoments_final", &comoments_final);
   m.def("dict_match", &dict_match);
   m.def("dict_match_layout", &dict_match_layout);
   m.def("part_agg", &part_agg);

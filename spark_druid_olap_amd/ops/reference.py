@@ -431,6 +431,32 @@ def group_variances(keys: torch.Tensor, v: torch.Tensor, ddof: int):
     return gids, torch.where(n > ddof, m2 / torch.clamp(n - ddof, min=1.0), nan)
 
 
+def group_comoments(keys: torch.Tensor, x: torch.Tensor, y: torch.Tensor, kind: str):
+    """Covariance (``kind`` "cov-samp" / "cov-pop") or Pearson correlation ("corr") by group in
+    float64, centred two-pass: (group keys ascending, value per group) of the (group key, x, y)
+    triples; NaN where the group holds too few rows (<= ddof; a correlation: < 2) or, for a
+    correlation, a column is constant.  NOT exact, as ``group_variances`` -- the engine's answer
+    wherever ops/csrc/comoments.hip does not apply."""
+    gids, inv, cnt = torch.unique(keys.to(torch.int64), return_inverse=True, return_counts=True)
+    x, y = x.to(torch.float64), y.to(torch.float64)
+    n = cnt.to(torch.float64)
+
+    def by_group(v):
+        return torch.zeros(len(gids), dtype=torch.float64, device=x.device).index_add_(0, inv, v)
+
+    dx, dy = x - (by_group(x) / n)[inv], y - (by_group(y) / n)[inv]
+    sdx, sdy = by_group(dx), by_group(dy)
+    cxy = by_group(dx * dy) - sdx * sdy / n
+    nan = torch.full_like(n, float("nan"))
+    if kind != "corr":
+        ddof = 1 if kind == "cov-samp" else 0
+        return gids, torch.where(n > ddof, cxy / torch.clamp(n - ddof, min=1.0), nan)
+    vx, vy = by_group(dx * dx) - sdx * sdx / n, by_group(dy * dy) - sdy * sdy / n
+    ok = (n > 1) & (vx > 0) & (vy > 0)
+    r = cxy / torch.sqrt(torch.where(ok, vx * vy, torch.ones_like(n)))
+    return gids, torch.where(ok, torch.clamp(r, -1.0, 1.0), nan)
+
+
 def run_reference_mask(prog) -> torch.Tensor:
     """Row ids passing the filter (select queries)."""
     dev = prog.ds.device

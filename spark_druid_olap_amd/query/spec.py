@@ -538,6 +538,32 @@ class VarianceAggregationSpec(Spec, _Decodable):
     type: str = "variance"
 
 
+@_register("aggregation", "covariance")
+@dataclass
+class CovarianceAggregationSpec(Spec, _Decodable):
+    """Covariance of two long / decimal / double metrics over the selected rows.  ``estimator``:
+    ``"sample"`` (n - 1 in the denominator, the default) or ``"population"`` (n).  The result is a
+    double, NaN for a group of fewer than two rows (one row, under ``"population"``: 0).  The type
+    name is this project's own: Druid's stats extension has no two-column aggregator."""
+    name: str
+    fieldName: str
+    fieldName2: str
+    estimator: str = "sample"
+    type: str = "covariance"
+
+
+@_register("aggregation", "correlation")
+@dataclass
+class CorrelationAggregationSpec(Spec, _Decodable):
+    """Pearson correlation of two long / decimal / double metrics over the selected rows: a double
+    in [-1, 1], NaN for a group of fewer than two rows or one in which a column is constant.  The
+    type name is this project's own, as ``covariance``."""
+    name: str
+    fieldName: str
+    fieldName2: str
+    type: str = "correlation"
+
+
 # ============================================================================ post aggregations
 @_register("postagg", "fieldAccess")
 @dataclass

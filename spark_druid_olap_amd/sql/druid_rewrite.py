@@ -698,7 +698,8 @@ class DruidRewriter:
                     continue
                 aggs.append(spec_)
                 r = A.Ref(A.new_id(), spec_.name, t)
-                if isinstance(spec_, (S.QuantilesAggregationSpec, S.VarianceAggregationSpec)):
+                if isinstance(spec_, (S.QuantilesAggregationSpec, S.VarianceAggregationSpec,
+                                      S.CovarianceAggregationSpec, S.CorrelationAggregationSpec)):
                     shared[id(spec_)] = r
                 drefs.append(r)
                 columns.append((spec_.name, t, part[2] if len(part) > 2 else "value"))
@@ -954,7 +955,41 @@ class DruidRewriter:
             return self._quantile_agg(pf, call, names, rolled)
         if n in VARIANCE_FUNCS:
             return self._variance_agg(pf, call, names, rolled)
+        if n in A.COMOMENT_FUNCS:
+            return self._comoment_agg(pf, call, names, rolled)
         raise NotPushable(f"aggregate {n} is not pushable")
+
+    def _comoment_agg(self, pf: PF, call: A.Call, names: "_Names", rolled: bool):
+        """corr / covar_samp / covar_pop over two plain long / decimal / double metrics -> ONE
+        ``correlation`` / ``covariance`` aggregator per (pair, kind) of the query.  An undefined
+        value is NaN, which the result conversion turns into NULL as the host plan's.  The co-moment
+        sums are per shard: a distributed session answers on the host."""
+        n = call.name
+        if call.distinct:
+            raise NotPushable(f"{n}(DISTINCT)")
+        if rolled or getattr(pf.table.info.datasource, "rollup", False):
+            raise NotPushable(f"{n} over a rolled-up datasource")
+        if self.session.engine.world.distributed:
+            raise NotPushable(f"{n} across ranks")
+        if len(call.args) != 2 or not all(isinstance(x, A.Ref) for x in call.args):
+            raise NotPushable(f"{n} over an expression")
+        fields = []
+        for x in call.args:
+            c = self._column(pf, x)
+            m = pf.table.info.datasource.metrics.get(c.druid_column) if c.is_metric else None
+            if m is None or m.sketch is not None or m.kind not in ("long", "decimal", "double"):
+                raise NotPushable(f"{n} over {c.column}: not a long / decimal / double metric")
+            if m.kind == "double" and (self.session.engine.deterministic or
+                                       bool(self.conf.typed("spark.sparklinedata.druid.deterministic"))):
+                raise NotPushable(f"{n} over the double metric {c.column} in deterministic mode")
+            fields.append(c.druid_column)
+        fields.sort()  # (the statistics are symmetric: corr(a, b) and corr(b, a) are one aggregator)
+        key = (fields[0], fields[1], n)
+        spec = names.comoments.get(key)
+        if spec is None:
+            spec = names.comoments[key] = S.CorrelationAggregationSpec(names.agg(), *fields) if n == "corr" else \
+                S.CovarianceAggregationSpec(names.agg(), *fields, "sample" if n == "covar_samp" else "population")
+        return [(spec, "double")], lambda rs: rs[0]
 
     def _variance_agg(self, pf: PF, call: A.Call, names: "_Names", rolled: bool):
         """stddev / stddev_samp / stddev_pop / variance / var_samp / var_pop over a plain long /
@@ -1516,6 +1551,7 @@ class _Names:
         self.used: Set[str] = set()
         self.quantiles: Dict[tuple, object] = {}  # (column, interpolate) -> its one quantiles aggregator
         self.variances: Dict[tuple, object] = {}  # (column, estimator) -> its one variance aggregator
+        self.comoments: Dict[tuple, object] = {}  # (column x, column y, function) -> its one aggregator
 
     def agg(self) -> str:
         self.n += 1

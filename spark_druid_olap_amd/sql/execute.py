@@ -1021,6 +1021,8 @@ def _agg_one(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, n: int, out_t:
         return pd.Series(cnt.astype(np.int64), dtype="Int64")
     if name in A.QUANTILE_FUNCS:
         return _agg_quantile(call, fr, codes, ng, out_t)
+    if name in A.COMOMENT_FUNCS:
+        return _agg_comoment(call, fr, codes, ng, out_t)
     args = [eval_series(a, fr) for a in call.args]
     x = args[0] if args else None
     if name == "count":
@@ -1088,6 +1090,34 @@ def _agg_one(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, n: int, out_t:
         r = g.agg(lambda v: list(v) if name == "collect_list" else sorted(set(v), key=str)).reindex(range(ng))
         return pd.Series(r.to_numpy(), dtype=object)
     raise AnalysisError(f"unsupported aggregate {name}")
+
+
+def _agg_comoment(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, out_t: str) -> pd.Series:
+    """corr / covar_samp / covar_pop per group (``ng`` = 1 without GROUP BY) over the rows where BOTH
+    arguments are non-NULL, a float64 centred two-pass.  NULL where the group holds too few such
+    rows (covar_samp and corr: fewer than 2; covar_pop: none) or, for corr, an argument is constant."""
+    x, y = (eval_series(a, fr) for a in call.args)
+    valid = ~(x.isna().to_numpy() | y.isna().to_numpy())
+    c = codes[valid] if len(codes) else np.zeros(int(valid.sum()), dtype=np.int64)
+    xv, yv = (v[valid].astype("float64").to_numpy(dtype=np.float64) for v in (x, y))
+    n = np.bincount(c, minlength=ng).astype(np.float64)
+
+    def by_group(v):
+        return np.bincount(c, weights=v, minlength=ng)
+
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dx, dy = xv - (by_group(xv) / n)[c], yv - (by_group(yv) / n)[c]
+        sdx, sdy = by_group(dx), by_group(dy)
+        cxy = by_group(dx * dy) - sdx * sdy / n
+        if call.name == "corr":
+            vx, vy = by_group(dx * dx) - sdx * sdx / n, by_group(dy * dy) - sdy * sdy / n
+            ok = (n > 1) & (vx > 0) & (vy > 0)
+            res = np.clip(cxy / np.sqrt(np.where(ok, vx * vy, 1.0)), -1.0, 1.0)
+        else:
+            ddof = 1.0 if call.name == "covar_samp" else 0.0
+            ok = n > ddof
+            res = cxy / np.where(ok, n - ddof, 1.0)
+    return to_series(pd.Series(np.where(ok, res, np.nan)), out_t)
 
 
 def _agg_quantile(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, out_t: str) -> pd.Series:

@@ -101,6 +101,20 @@ def quantile_type(call: A.Call) -> str:
     return "array" if is_arr else ("double" if interp else t)
 
 
+def comoment_type(call: A.Call) -> str:
+    """corr / covar_samp / covar_pop: exactly two numeric arguments, no DISTINCT; a double."""
+    n = call.name
+    if call.distinct:
+        raise AnalysisError(f"{n}(DISTINCT ...) is not supported")
+    if len(call.args) != 2:
+        raise AnalysisError(f"{n} takes exactly 2 arguments, got {len(call.args)}")
+    for a in call.args:
+        t = typeof(a)
+        if base(t) not in INTEGRAL and base(t) not in ("double", "float", "decimal"):
+            raise AnalysisError(f"{n} over the non-numeric type {t}")
+    return "double"
+
+
 def agg_type(name: str, ts: Sequence[str]) -> str:
     if name == "count" or name == "approx_count_distinct":
         return "bigint"
@@ -157,6 +171,8 @@ def typeof(e: A.Expr) -> str:
         return "boolean"
     if isinstance(e, A.WindowExpr):
         f = e.func
+        if f.name in A.COMOMENT_FUNCS:
+            raise AnalysisError(f"{f.name} over a window is not supported")
         if f.name in ("rank", "dense_rank", "row_number", "ntile"):
             return "int"
         if f.name in ("percent_rank", "cume_dist"):
@@ -167,6 +183,8 @@ def typeof(e: A.Expr) -> str:
     if isinstance(e, A.Call):
         if e.name in A.QUANTILE_FUNCS:
             return quantile_type(e)
+        if e.name in A.COMOMENT_FUNCS:
+            return comoment_type(e)
         ts = [typeof(a) for a in e.args]
         if e.is_agg:
             return agg_type(e.name, ts)
