@@ -1486,7 +1486,7 @@ class PreparedEmit:
         ep.aops = [{"kind": D.A_ROWID, "col": -1, "expr": None, "filter": None, "slot": 0, "hll": -1}]
         ep.slots = [(D.S_SUM_I, 0)]
         ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
-        ep.comoments = []
+        ep.comoments, ep.extremes = [], []
         ep.presence_only = False
         self.prog = ep
         self.dev = prog.ds.device
@@ -1558,7 +1558,7 @@ def theta_producer_prog(prog: ScanProgram, cols: List[str]) -> ScanProgram:
                for i, c in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(cols)
     ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
-    ep.comoments = []
+    ep.comoments, ep.extremes = [], []
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("theta: program not eligible")
@@ -1726,10 +1726,11 @@ class PreparedTheta:
         return out
 
 
-def quantile_producer_prog(prog: ScanProgram, cols: List[str]) -> ScanProgram:
+def quantile_producer_prog(prog: ScanProgram, cols: List[str], rowid: bool = False) -> ScanProgram:
     """The scan program of a quantile producer: ``prog``'s filter, ranges and group key, one A_QVAL
     aggregator (the value as an order-preserving u64, two record words) per distinct quantile
-    column, no other aggregator.  RuntimeError where it does not apply."""
+    column, before them one A_ROWID word when ``rowid``, no other aggregator.  RuntimeError where it
+    does not apply."""
     import copy
 
     from ..ops import jit as J
@@ -1741,11 +1742,13 @@ def quantile_producer_prog(prog: ScanProgram, cols: List[str]) -> ScanProgram:
             raise RuntimeError("quantile: fused only over long / decimal / double metrics")
     ep = copy.copy(prog)
     ep.pcols, ep.fcols, ep.section = list(prog.pcols), list(prog.fcols), "p"
-    ep.aops = [{"kind": D.A_QVAL, "col": ep.col(c), "expr": None, "filter": None, "slot": i, "hll": -1}
-               for i, c in enumerate(cols)]
-    ep.slots = [(D.S_SUM_I, 0)] * len(cols)
+    r = 1 if rowid else 0
+    ep.aops = [{"kind": D.A_ROWID, "col": -1, "expr": None, "filter": None, "slot": 0, "hll": -1}][:r]
+    ep.aops += [{"kind": D.A_QVAL, "col": ep.col(c), "expr": None, "filter": None, "slot": r + i, "hll": -1}
+                for i, c in enumerate(cols)]
+    ep.slots = [(D.S_SUM_I, 0)] * len(ep.aops)
     ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
-    ep.comoments = []
+    ep.comoments, ep.extremes = [], []
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("quantile: program not eligible")
@@ -1760,16 +1763,18 @@ QSEL_MAX_HIST_BYTES = 512 << 20
 class _QvalRecords:
     """ONE JIT producer pass (ops/jit.py A_QVAL) that writes (u32 group key, ordered u64 value per
     column of ``cols``) records of the selected rows into its chunk regions: what the quantile
-    select and the moment sums read.  ``what`` names the caller in the RuntimeErrors."""
+    select and the moment sums read.  ``rowid``: the u32 row id (A_ROWID) follows the key, what the
+    max_by / min_by extremes read.  ``what`` names the caller in the RuntimeErrors."""
 
-    def __init__(self, prog: ScanProgram, cols: List[str], max_g: int, what: str):
+    def __init__(self, prog: ScanProgram, cols: List[str], max_g: int, what: str, rowid: bool = False):
         from .lower import lds_layout
 
         ds = prog.ds
         if prog.empty or not (0 < prog.G <= max_g):
             raise RuntimeError(f"{what}: program not eligible")
         self.cols = cols
-        ep = quantile_producer_prog(prog, self.cols)
+        self.hdr = 2 if rowid else 1  # record words before the first value
+        ep = quantile_producer_prog(prog, self.cols, rowid)
         self.prog, self.dev, self.G = ep, ds.device, int(prog.G)
         self.jit = _jit_for(ep, D.M_PART, False, 1 << prog.hll_p)
         if self.jit is None:
@@ -1779,7 +1784,7 @@ class _QvalRecords:
                  wave_bytes=wave_bytes)
         self.nch = int(d[0]["total_chunks"])
         self.grid = _grid(self.dev, self.nch, self.jit.lay.total, self.jit)
-        self.rw = 1 + 2 * len(self.cols)
+        self.rw = self.hdr + 2 * len(self.cols)
         cap = self.nch * D.CHUNK_ROWS
         if cap * self.rw >= (1 << 32):
             raise RuntimeError(f"{what}: shard too large for u32 offsets")
@@ -1789,7 +1794,7 @@ class _QvalRecords:
 
     def voff(self, col: str) -> int:
         """Record word at which ``col``'s value starts."""
-        return 1 + 2 * self.cols.index(col)
+        return self.hdr + 2 * self.cols.index(col)
 
     def produce(self, nat, st, slab, pend) -> tuple:
         """Launch the producer into ``slab`` (region ends into ``pend``); the region arguments the
@@ -2030,6 +2035,92 @@ class PreparedComoments(_QvalRecords):
             PART_POOL.release(slab)
 
 
+EXT_PACKED, EXT_WIDE_VAL, EXT_WIDE_ROW = range(3)  # ops/csrc/extreme.h ExtMode
+EXT_MAX, EXT_MIN, EXT_BOTH = 1, 2, 3              # ... ExtDirs (the tiers are MOM_TIERS)
+EXT_TYPES = {torch.int8: 0, torch.uint8: 1, torch.int16: 2, torch.int32: 3, torch.int64: 4, torch.float32: 5,
+             torch.float64: 6}                     # ... ExtType
+
+
+def time_sorted(ds) -> bool:
+    """Whether the shard's rows are stored in time order (checked once per datasource): ordering
+    by ``__time`` is then ordering by the row id."""
+    ok = ds.__dict__.get("_time_sorted")
+    if ok is None:
+        t = np.asarray(ds.time_host)
+        ok = ds._time_sorted = bool(np.all(t[1:] >= t[:-1]))
+    return ok
+
+
+class PreparedExtremes(_QvalRecords):
+    """``maxBy`` / ``minBy`` aggregators pushed into the scan: ONE producer pass writes (u32 group
+    key, u32 row id, ordered u64 value per distinct ordering metric) records, then per distinct
+    ordering column ONE accumulation of ops/csrc/extreme.hip -- a u64 key per (group, direction) whose
+    integer max / min is the lexicographic extreme of (value, row id); every aggregator over that
+    column shares it, the payloads are gathered by the decoded row ids in one finalise launch.
+    Columns stored in at most 32 bits and ``__time`` (the row id alone: the shard must be time-sorted)
+    take one packed pass, int64 and double columns two (the value's extreme, then the row's among the
+    records that hold it).  Bitwise reproducible.  Nothing is read back before the result copy.
+    G <= ``max_g``."""
+
+    def __init__(self, prog: ScanProgram, extremes: list, max_g: int):
+        from .lower import column_tensor
+
+        ds = prog.ds
+        if any(by == "__time" for _, _, by, _ in extremes) and not time_sorted(ds):
+            raise RuntimeError("extremes: the shard is not time-sorted")
+        super().__init__(prog, sorted({by for _, _, by, _ in extremes if by != "__time"}), max_g, "extremes", rowid=True)
+        # per distinct ordering column: (value word offset or 0, packed, directions)
+        self.passes = {}
+        for _, _, by, is_max in extremes:
+            t = None if by == "__time" else column_tensor(ds, by)
+            packed = t is None or (not t.dtype.is_floating_point and t.element_size() <= 4)
+            dirs = (EXT_MAX if is_max else EXT_MIN) | (self.passes[by][2] if by in self.passes else 0)
+            self.passes[by] = (0 if t is None else self.voff(by), packed, dirs)
+        # per aggregator: (ordering column, is max, payload column tensor, its ExtType, decimal divisor or 0)
+        self.sel = []
+        for _, x, by, is_max in extremes:
+            m, t = ds.metrics[x], column_tensor(ds, x)
+            if t.dtype not in EXT_TYPES or not t.is_contiguous():
+                raise RuntimeError("extremes: payload column type")
+            self.sel.append((by, bool(is_max), t, EXT_TYPES[t.dtype],
+                             float(10 ** int(m.scale)) if m.kind == "decimal" else 0.0))
+        self.rows = int(min(t.numel() for _, _, t, _, _ in self.sel))
+        self.tiers = []  # (per distinct ordering column of the last run: the tier its passes took)
+
+    def values(self) -> list:
+        """Per aggregator its payloads [G] (host: int64 for long payloads, else float64; 0 where the
+        group holds no selected row)."""
+        nat, st = native.load(), native._stream(self.dev)
+        dev, G = self.dev, self.G
+        pend = torch.empty(max(1, self.nch), dtype=torch.int32, device=dev)
+        slab = PART_POOL.acquire(dev, self.words)
+        try:
+            regions = self.produce(nat, st, slab, pend)
+            recs = slab.recs1.data_ptr()
+            states, self.tiers = {}, []
+            for by, (voff, packed, dirs) in self.passes.items():
+                D = 2 if dirs == EXT_BOTH else 1
+                a = torch.empty(G * D, dtype=torch.int64, device=dev)
+                tier = nat.extreme_accum(recs, self.rw, voff, *regions, EXT_PACKED if packed else EXT_WIDE_VAL, dirs, -1,
+                                         0, a.data_ptr(), st)
+                if not packed:
+                    b = torch.empty(G * D, dtype=torch.int64, device=dev)
+                    nat.extreme_accum(recs, self.rw, voff, *regions, EXT_WIDE_ROW, dirs, -1, a.data_ptr(), b.data_ptr(), st)
+                    a = b
+                states[by] = (a, D)
+                self.tiers.append(MOM_TIERS[tier])
+            outs, args = [], []
+            for by, is_max, t, typ, div in self.sel:
+                a, D = states[by]
+                out = torch.empty(G, dtype=torch.int64, device=dev)
+                outs.append(out if typ < 5 and not div else out.view(torch.float64))
+                args.append((t.data_ptr(), a.data_ptr(), out.data_ptr(), div, D, 0 if is_max else D - 1, typ))
+            nat.extreme_final(args, G, self.rows, st)
+            return [o.cpu().numpy() for o in outs]
+        finally:
+            PART_POOL.release(slab)
+
+
 def distinct_producer_prog(prog: ScanProgram, cols: list) -> ScanProgram:
     """The scan program of a distinct producer: ``prog``'s filter, ranges and group key, one
     A_DISTINCT aggregator (the dimension's dictionary id, one record word) per (column, aggregator
@@ -2044,7 +2135,7 @@ def distinct_producer_prog(prog: ScanProgram, cols: list) -> ScanProgram:
                 "filt_off": off, "filt_len": n} for i, (c, (off, n)) in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(cols)
     ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
-    ep.comoments = []
+    ep.comoments, ep.extremes = [], []
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("distinct: program not eligible")

@@ -501,11 +501,14 @@ class PreparedQuery:
                 tiers = self._distinct(self._full_prog, cols)
                 self._moments(self._full_prog, cols)
                 co_tiers = self._comoments(self._full_prog, cols)
+                ext_tiers = self._extremes(self._full_prog, cols)
                 res = self._post(prog, cols)
                 if tiers:
                     res.stats["distinct_count_device"] = tiers
                 if co_tiers:
                     res.stats["comoments_device"] = co_tiers
+                if ext_tiers:
+                    res.stats["extremes_device"] = ext_tiers
             t4 = time.perf_counter()
             res.stats.update(scan_ms=(t1 - t0) * 1e3, merge_ms=(t2 - t1) * 1e3, finalize_ms=(t3 - t2) * 1e3,
                              post_ms=(t4 - t3) * 1e3)
@@ -1342,6 +1345,69 @@ class PreparedQuery:
         if cp is False:
             return None
         return cp.values()
+
+    # ------------------------------------------------------------------ max_by / min_by
+    def _extremes(self, prog: ScanProgram, cols: Dict[str, np.ndarray]) -> Optional[list]:
+        """``maxBy`` / ``minBy`` aggregators: per group the payload of the selected row at the
+        lexicographic extreme of (ordering value, row id), an int64 (long payloads) or float64 column
+        that HAVING, ordering and post-aggregations read like a sum.  On the native GPU engine the
+        packed-key extremes answer (engine/device_exec.py PreparedExtremes); everywhere else -- CPU,
+        the reference executor, hashed keys, more than QUANTILE_SELECT_MAX_G groups, ``__time`` over a
+        shard that is not time-sorted -- torch takes the same extreme (ops/reference.py
+        group_extremes): both are exact.  Returns the tier per ordering column when the device
+        answered (the result's ``extremes_device`` stats entry), else None."""
+        if not prog.extremes:
+            return None
+        gid_order = np.asarray(cols["__gid__"], dtype=np.int64)
+        fused = self._extremes_fused(prog)
+        if fused is not None:
+            for (name, _, _, _), res in zip(prog.extremes, fused):
+                ok = (gid_order >= 0) & (gid_order < len(res))
+                cols[name] = np.where(ok, res[np.clip(gid_order, 0, max(0, len(res) - 1))], 0).astype(res.dtype)
+            return list(self._extremes_prep.tiers)
+        from ..ops.reference import _rows, compute_keys, eval_bexpr, group_extremes
+        from .lower import column_tensor
+
+        ds = self.ds
+        rows = _rows(prog) if not prog.empty else torch.zeros(0, dtype=torch.int64, device=ds.device)
+        if rows.numel():
+            rows = rows[eval_bexpr(prog, prog.bexpr, rows)]
+        keys = compute_keys(prog, rows)
+        picks = {}  # (ordering column, direction) -> (group keys, the row at the extreme)
+        for name, x, by, is_max in prog.extremes:
+            if (by, is_max) not in picks:
+                y = ds.time[rows] if by == "__time" else column_tensor(ds, by)[rows]
+                gids, at = group_extremes(keys, y, rows, is_max)
+                picks[(by, is_max)] = (gids.cpu().numpy(), at)
+            gids, at = picks[(by, is_max)]
+            m = ds.metrics[x]
+            val = column_tensor(ds, x)[at].cpu().numpy()
+            val = val.astype(np.int64) if m.kind == "long" else val.astype(np.float64)
+            if m.kind == "decimal":
+                val = val / float(10 ** int(m.scale))
+            pos = np.clip(np.searchsorted(gids, gid_order), 0, max(0, len(gids) - 1))
+            cols[name] = np.where(gids[pos] == gid_order, val[pos], 0).astype(val.dtype) if len(gids) else \
+                np.zeros(len(gid_order), dtype=val.dtype)
+        return None
+
+    def _extremes_fused(self, prog: ScanProgram) -> Optional[list]:
+        """Per maxBy / minBy aggregator its payloads [G] from the device extremes, or None where they
+        do not apply (CPU, hashed or ineligible keys, too many groups, an empty shard, ordering by
+        time over a shard that is not time-sorted)."""
+        if prog.empty or self.ds.device.type != "cuda" or not self.engine.use_native:
+            return None
+        ep = self.__dict__.get("_extremes_prep")
+        if ep is None:
+            try:
+                from .device_exec import PreparedExtremes
+
+                ep = PreparedExtremes(prog, prog.extremes, QUANTILE_SELECT_MAX_G)
+            except RuntimeError:
+                ep = False
+            self._extremes_prep = ep
+        if ep is False:
+            return None
+        return ep.values()
 
     # ------------------------------------------------------------------ post processing
     def _post(self, prog: ScanProgram, cols: Dict[str, np.ndarray]) -> QueryResult:

@@ -374,6 +374,8 @@ class ScanProgram:
     moments: List[Tuple[str, str, int]] = field(default_factory=list)
     # covariances / correlations: (name, metric x, metric y, kind: "cov-pop" | "cov-samp" | "corr")
     comoments: List[Tuple[str, str, str, str]] = field(default_factory=list)
+    # max_by / min_by: (name, payload metric, ordering metric or "__time", is max)
+    extremes: List[Tuple[str, str, str, bool]] = field(default_factory=list)
     luts: Dict[str, torch.Tensor] = field(default_factory=dict)       # dim -> f64 value per dictionary id
     lut_ptrs: Dict[float, torch.Tensor] = field(default_factory=dict)  # E_LUT operand -> its table
     # grouping keys functionally determined by a packed key: (key, index of determinant in keys,
@@ -392,10 +394,11 @@ class ScanProgram:
     @property
     def needs_rows(self) -> bool:
         """Some aggregator reads the selected rows themselves (theta KMV, order statistics, exact
-        distinct counts, variances, covariances), not an accumulator: strategies that keep only
-        accumulators decline, the executor answers it after the scan (engine/executor.py _theta /
-        _quantile / _distinct / _moments / _comoments)."""
-        return bool(self.thetas or self.quantiles or self.distincts or self.moments or self.comoments)
+        distinct counts, variances, covariances, values at an extreme), not an accumulator: strategies
+        that keep only accumulators decline, the executor answers it after the scan
+        (engine/executor.py _theta / _quantile / _distinct / _moments / _comoments / _extremes)."""
+        return bool(self.thetas or self.quantiles or self.distincts or self.moments or self.comoments or
+                    self.extremes)
 
     @property
     def nhll_total(self) -> int:
@@ -1408,6 +1411,26 @@ class Lowerer:
             kind = "corr" if what == "correlation" else "cov-samp" if a.estimator == "sample" else "cov-pop"
             prog.comoments.append((a.name, a.fieldName, a.fieldName2, kind))
             prog.aggs.append(AggOut(a.name, "moment", out_type="double", combine="moment"))
+            return
+        if isinstance(a, (S.MaxByAggregationSpec, S.MinByAggregationSpec)):
+            what = a.type
+            if self.world is not None and self.world.distributed:
+                # (the keys are max / min mergeable, but the payload gather then needs the owning rank)
+                raise LoweringError(f"{what} aggregators are not answered across ranks")
+            for f in (a.fieldName, a.byFieldName):
+                if f == "__time" and f is a.byFieldName:
+                    continue  # (the ordering field only: the shard's storage order)
+                m = ds.metrics.get(f)
+                if m is None:
+                    raise LoweringError(f"{what} over {f!r}: not a metric")
+                if m.sketch is not None or m.kind not in ("long", "double", "decimal"):
+                    raise LoweringError(f"{what} over the sketch metric {f!r}")
+            if filt is not None:
+                raise LoweringError(f"{what} inside a filtered aggregator is not supported")
+            # (an integer max / min per group: bitwise reproducible for double columns too)
+            prog.extremes.append((a.name, a.fieldName, a.byFieldName, isinstance(a, S.MaxByAggregationSpec)))
+            prog.aggs.append(AggOut(a.name, "moment", combine="moment",
+                                    out_type="long" if ds.metrics[a.fieldName].kind == "long" else "double"))
             return
         raise LoweringError(f"unsupported aggregator {type(a).__name__}")
 

@@ -26,6 +26,7 @@
 #include "distinct.h"
 #include "moments.h"
 #include "comoments.h"
+#include "extreme.h"
 
 namespace sdo {
 template <int U>
@@ -157,6 +158,24 @@ __global__ void co_global_regions_kernel(const uint32_t* __restrict__ recs, int 
 __global__ void co_mean_kernel(const uint64_t* sum, int G, double* mean);
 __global__ void co_final_kernel(const uint64_t* a, const uint64_t* b, int G, int mode, int sq, int kind, int ddof,
                                 double div, double* out);
+// extreme.hip (shapes: extreme.h)
+template <int MODE, int DIRS>
+__global__ void ext_few_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff,
+                                       const uint32_t* __restrict__ seg_lo, const uint32_t* __restrict__ seg_hi,
+                                       int64_t nseg, uint32_t G, const uint64_t* __restrict__ ext,
+                                       uint64_t* __restrict__ state);
+template <int MODE, int DIRS>
+__global__ void ext_lds_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff,
+                                       const uint32_t* __restrict__ seg_lo, const uint32_t* __restrict__ seg_hi,
+                                       int64_t nseg, uint32_t g0, uint32_t GL, const uint64_t* __restrict__ ext,
+                                       uint64_t* __restrict__ state);
+template <int MODE, int DIRS>
+__global__ void ext_global_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff,
+                                          const uint32_t* __restrict__ seg_lo, const uint32_t* __restrict__ seg_hi,
+                                          int64_t nseg, uint32_t G, const uint64_t* __restrict__ ext,
+                                          uint64_t* __restrict__ state);
+__global__ void ext_init_kernel(uint64_t* state, int64_t n, int dirs);
+__global__ void ext_final_kernel(ExtFinalArgs a);
 // p2p.hip (P2PArgs: p2p.h)
 __global__ void p2p_merge_kernel(P2PArgs a);
 }  // namespace sdo
@@ -1227,6 +1246,96 @@ static void comoments_final(uint64_t a, uint64_t b, int64_t G, int mode, bool sq
 }
 
 // ---------------------------------------------------------------------------------------------
+// max_by / min_by: per-group packed-key extremes over (key, row id, ordered values ...) records
+// (extreme.hip).  One accumulation pass of `mode` (extreme.h ExtMode) for the directions `dirs`
+// (ExtDirs) over the value at `voff` (0: none, the ordering is the row id alone -- EXT_PACKED only)
+// into the [G][D] u64 `state`, which is set to its identities first.  EXT_WIDE_ROW reads pass 1's
+// state (`ext`).  `tier` -1 picks the tier from G (extreme.h ext_tier); 0..2 asks for one that holds
+// G.  Returns the tier used.
+template <int MODE, int DIRS>
+static void ext_launch(int tier, unsigned grid, hipStream_t s, const uint32_t* recs, int rw, int voff,
+                       const uint32_t* seg_lo, const uint32_t* seg_hi, int64_t nseg, uint32_t G, const uint64_t* ext,
+                       uint64_t* state) {
+  if (tier == sdo::EXT_TIER_FEW) {
+    hipLaunchKernelGGL((sdo::ext_few_regions_kernel<MODE, DIRS>), dim3(grid), dim3(256), 0, s, recs, rw, voff, seg_lo,
+                       seg_hi, nseg, G, ext, state);
+  } else if (tier == sdo::EXT_TIER_LDS) {
+    // one pass per key slice of (nearly) equal size, each table within the LDS budget
+    const uint32_t cap = (uint32_t)sdo::ext_lds_groups(DIRS);
+    const uint32_t slices = (G + cap - 1) / cap, GL = (G + slices - 1) / slices;
+    for (uint32_t g0 = 0; g0 < G; g0 += GL) {
+      const uint32_t n = std::min(GL, G - g0);
+      hipLaunchKernelGGL((sdo::ext_lds_regions_kernel<MODE, DIRS>), dim3(grid), dim3(256),
+                         n * (size_t)(8 * sdo::ext_words(DIRS)), s, recs, rw, voff, seg_lo, seg_hi, nseg, g0, n, ext,
+                         state);
+    }
+  } else {
+    hipLaunchKernelGGL((sdo::ext_global_regions_kernel<MODE, DIRS>), dim3(grid), dim3(256), 0, s, recs, rw, voff,
+                       seg_lo, seg_hi, nseg, G, ext, state);
+  }
+}
+
+static int extreme_accum(uint64_t recs, int rw, int voff, uint64_t seg_lo, uint64_t seg_hi, int64_t nseg, int64_t G,
+                         int mode, int dirs, int tier, uint64_t ext, uint64_t state, uint64_t stream) {
+  if (G <= 0 || G > (1 << 20)) throw std::invalid_argument("extreme_accum: 1..2^20 groups");
+  if (mode < sdo::EXT_PACKED || mode > sdo::EXT_WIDE_ROW || dirs < sdo::EXT_MAX || dirs > sdo::EXT_BOTH)
+    throw std::invalid_argument("extreme_accum: mode");
+  if (rw < 2 || (voff == 0 ? mode != sdo::EXT_PACKED : (voff < 2 || voff + 2 > rw)))
+    throw std::invalid_argument("extreme_accum: record layout");
+  if (nseg < 0 || !state || (mode == sdo::EXT_WIDE_ROW && !ext)) throw std::invalid_argument("extreme_accum: arguments");
+  const int fit = sdo::ext_tier(dirs, G);
+  if (tier < 0) tier = fit;
+  if (tier > sdo::EXT_TIER_GLOBAL || tier < fit) throw std::invalid_argument("extreme_accum: tier does not hold G");
+  const int64_t nw = G * sdo::ext_words(dirs);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(sdo::ext_init_kernel, dim3(grid_for(nw, 256, 4096)), dim3(256), 0, s, (uint64_t*)state, nw, dirs);
+  check(hipGetLastError(), "ext_init_kernel launch");
+  if (nseg == 0) return tier;
+  // (the grids of moments_accum: few / lds workgroups end with a flush onto the same global words)
+  const unsigned grid = (unsigned)std::min<int64_t>(nseg, tier == sdo::EXT_TIER_GLOBAL ? 4096 : 1024);
+  const uint32_t* r = (const uint32_t*)recs;
+  const uint32_t *lo = (const uint32_t*)seg_lo, *hi = (const uint32_t*)seg_hi;
+  const uint64_t* ex = (const uint64_t*)ext;
+  uint64_t* st = (uint64_t*)state;
+#define SDO_EXT_CASE(M, DR) ext_launch<sdo::M, sdo::DR>(tier, grid, s, r, rw, voff, lo, hi, nseg, (uint32_t)G, ex, st)
+#define SDO_EXT_DIRS(M) \
+  (dirs == sdo::EXT_MAX ? SDO_EXT_CASE(M, EXT_MAX) : dirs == sdo::EXT_MIN ? SDO_EXT_CASE(M, EXT_MIN) : SDO_EXT_CASE(M, EXT_BOTH))
+  switch (mode) {
+    case sdo::EXT_PACKED: SDO_EXT_DIRS(EXT_PACKED); break;
+    case sdo::EXT_WIDE_VAL: SDO_EXT_DIRS(EXT_WIDE_VAL); break;
+    default: SDO_EXT_DIRS(EXT_WIDE_ROW); break;
+  }
+#undef SDO_EXT_DIRS
+#undef SDO_EXT_CASE
+  check(hipGetLastError(), "extreme accumulation launch");
+  return tier;
+}
+
+// Per payload (column pointer, its [G][D] state, out [G], div, D, word, extreme.h ExtType): out[g] =
+// the payload of the row whose id word `word` of group g's state holds -- int64 for integer payloads
+// (div 0), f64 for doubles and, divided by div = 10^scale, decimals.  `rows`: rows of the columns.
+using ExtTuple = std::tuple<uint64_t, uint64_t, uint64_t, double, int, int, int>;
+static void extreme_final(std::vector<ExtTuple> payloads, int64_t G, int64_t rows, uint64_t stream) {
+  if (G <= 0 || G > (1 << 20) || rows < 0) throw std::invalid_argument("extreme_final: arguments");
+  for (size_t at = 0; at < payloads.size(); at += sdo::EXT_FINAL_MAX) {
+    sdo::ExtFinalArgs a{};
+    a.n = (int32_t)std::min<size_t>(sdo::EXT_FINAL_MAX, payloads.size() - at);
+    a.G = (int32_t)G;
+    a.rows = rows;
+    for (int i = 0; i < a.n; ++i) {
+      const auto& [col, state, out, div, D, word, type] = payloads[at + i];
+      if (!col || !state || !out || D < 1 || D > 2 || word < 0 || word >= D || type < sdo::EXT_I8 ||
+          type > sdo::EXT_F64 || div < 0.0)
+        throw std::invalid_argument("extreme_final: payload");
+      a.p[i] = sdo::ExtPayload{(const void*)col, (const uint64_t*)state, (uint64_t*)out, div, D, word, type, 0};
+    }
+    hipLaunchKernelGGL(sdo::ext_final_kernel, dim3((unsigned)((G + 255) / 256), (unsigned)a.n), dim3(256), 0,
+                       (hipStream_t)stream, a);
+    check(hipGetLastError(), "ext_final_kernel launch");
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // LIKE / contains / fragment over a dictionary's device text heap (dict_match.hip): bit e of `out`
 // says entry e matches `program` (a packed DmProgram); when the program folds case, bit e of
 // `nonascii` says entry e holds a byte >= 0x80 (the host re-evaluates those).  `heap` is 16-byte
@@ -1533,6 +1642,8 @@ PYBIND11_MODULE(_sdo_native, m) {
   m.def("comoments_accum", &comoments_accum);
   m.def("comoments_mean", &comoments_mean);
   m.def("comoments_final", &comoments_final);
+  m.def("extreme_accum", &extreme_accum);
+  m.def("extreme_final", &extreme_final);
   m.def("dict_match", &dict_match);
   m.def("dict_match_layout", &dict_match_layout);
   m.def("part_agg", &part_agg);

@@ -457,6 +457,23 @@ def group_comoments(keys: torch.Tensor, x: torch.Tensor, y: torch.Tensor, kind: 
     return gids, torch.where(ok, torch.clamp(r, -1.0, 1.0), nan)
 
 
+def group_extremes(keys: torch.Tensor, y: torch.Tensor, rows: torch.Tensor, is_max: bool):
+    """max_by / min_by by group: (group keys ascending, the row id at the lexicographic maximum /
+    minimum of (y, row id)) of the (group key, ordering value y, row id) triples -- among rows that
+    tie on y the last (max) or first (min) row.  Doubles order as the kernels' f2ord orders their
+    bits.  Exact, as ops/csrc/extreme.hip: the engine's answer wherever that does not apply."""
+    gids, inv = torch.unique(keys.to(torch.int64), return_inverse=True)
+    if y.dtype.is_floating_point:
+        b = y.to(torch.float64).view(torch.int64)
+        y = torch.where(b >= 0, b, b ^ 0x7FFFFFFFFFFFFFFF)
+    y, rows = y.to(torch.int64), rows.to(torch.int64)
+    how = "amax" if is_max else "amin"
+    ext = torch.zeros(len(gids), dtype=torch.int64, device=y.device).scatter_reduce(0, inv, y, how, include_self=False)
+    tied = y == ext[inv]
+    return gids, torch.zeros(len(gids), dtype=torch.int64, device=y.device).scatter_reduce(
+        0, inv[tied], rows[tied], how, include_self=False)
+
+
 def run_reference_mask(prog) -> torch.Tensor:
     """Row ids passing the filter (select queries)."""
     dev = prog.ds.device

@@ -564,6 +564,33 @@ class CorrelationAggregationSpec(Spec, _Decodable):
     type: str = "correlation"
 
 
+@dataclass
+class _ExtremeBySpec(Spec, _Decodable):
+    name: str
+    fieldName: str
+    byFieldName: str
+
+
+@_register("aggregation", "maxBy")
+@dataclass
+class MaxByAggregationSpec(_ExtremeBySpec):
+    """``fieldName`` (a long / decimal / double metric) of the selected row with the largest
+    ``byFieldName`` (such a metric, or ``"__time"``); among rows that tie, the last in the shard's
+    storage order.  Ordered by ``"__time"`` this is Druid's longLast / doubleLast.  The result has
+    the payload's type (long, or double for double and decimal payloads).  The type name is this
+    project's own: Druid has no two-column aggregator."""
+    type: str = "maxBy"
+
+
+@_register("aggregation", "minBy")
+@dataclass
+class MinByAggregationSpec(_ExtremeBySpec):
+    """``fieldName`` of the selected row with the smallest ``byFieldName``; among rows that tie, the
+    first in storage order (ordered by ``"__time"``: Druid's longFirst / doubleFirst).  The type
+    name is this project's own, as ``maxBy``."""
+    type: str = "minBy"
+
+
 # ============================================================================ post aggregations
 @_register("postagg", "fieldAccess")
 @dataclass

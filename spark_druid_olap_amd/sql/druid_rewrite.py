@@ -699,7 +699,8 @@ class DruidRewriter:
                 aggs.append(spec_)
                 r = A.Ref(A.new_id(), spec_.name, t)
                 if isinstance(spec_, (S.QuantilesAggregationSpec, S.VarianceAggregationSpec,
-                                      S.CovarianceAggregationSpec, S.CorrelationAggregationSpec)):
+                                      S.CovarianceAggregationSpec, S.CorrelationAggregationSpec,
+                                      S.MaxByAggregationSpec, S.MinByAggregationSpec)):
                     shared[id(spec_)] = r
                 drefs.append(r)
                 columns.append((spec_.name, t, part[2] if len(part) > 2 else "value"))
@@ -957,6 +958,8 @@ class DruidRewriter:
             return self._variance_agg(pf, call, names, rolled)
         if n in A.COMOMENT_FUNCS:
             return self._comoment_agg(pf, call, names, rolled)
+        if n in A.EXTREME_FUNCS:
+            return self._extreme_agg(pf, call, names, rolled)
         raise NotPushable(f"aggregate {n} is not pushable")
 
     def _comoment_agg(self, pf: PF, call: A.Call, names: "_Names", rolled: bool):
@@ -990,6 +993,44 @@ class DruidRewriter:
             spec = names.comoments[key] = S.CorrelationAggregationSpec(names.agg(), *fields) if n == "corr" else \
                 S.CovarianceAggregationSpec(names.agg(), *fields, "sample" if n == "covar_samp" else "population")
         return [(spec, "double")], lambda rs: rs[0]
+
+    def _extreme_agg(self, pf: PF, call: A.Call, names: "_Names", rolled: bool):
+        """max_by / min_by (x, y) -> ONE ``maxBy`` / ``minBy`` aggregator per (x, y, function) of the
+        query: x a plain long / decimal / double metric, y such a metric or the datasource's time
+        column (``byFieldName`` ``__time``, where min / max over it are recognised:
+        ``_time_valued_agg``).  The result has x's type.  The payload gather is per shard: a
+        distributed session answers on the host."""
+        n = call.name
+        if call.distinct:
+            raise NotPushable(f"{n}(DISTINCT)")
+        if rolled or getattr(pf.table.info.datasource, "rollup", False):
+            raise NotPushable(f"{n} over a rolled-up datasource")
+        if self.session.engine.world.distributed:
+            raise NotPushable(f"{n} across ranks")
+        if len(call.args) != 2:
+            raise NotPushable(f"{n} takes 2 arguments")
+        x = call.args[0]
+        y, casted = _strip_time_casts(call.args[1])
+        if not isinstance(x, A.Ref) or not isinstance(y, A.Ref):
+            raise NotPushable(f"{n} over an expression")
+        fields = []
+        for e in (x, y):
+            c = self._column(pf, e)
+            if e is y and c.is_time and (casted or base(typeof(y)) in ("date", "timestamp")):
+                fields.append("__time")
+                continue
+            m = pf.table.info.datasource.metrics.get(c.druid_column) if c.is_metric and not (e is y and casted) else None
+            if m is None or m.sketch is not None or m.kind not in ("long", "decimal", "double"):
+                raise NotPushable(f"{n} over {c.column}: not a long / decimal / double metric")
+            fields.append(c.druid_column)
+        key = (fields[0], fields[1], n)
+        spec = names.extremes.get(key)
+        if spec is None:
+            cls = S.MaxByAggregationSpec if n == "max_by" else S.MinByAggregationSpec
+            spec = names.extremes[key] = cls(names.agg(), *fields)
+        xt = typeof(x)
+        long_ = pf.table.info.datasource.metrics[fields[0]].kind == "long" and base(xt) in INTEGRAL
+        return [(spec, xt if long_ else "double")], lambda rs: rs[0]  # (cast to x's type by the caller)
 
     def _variance_agg(self, pf: PF, call: A.Call, names: "_Names", rolled: bool):
         """stddev / stddev_samp / stddev_pop / variance / var_samp / var_pop over a plain long /
@@ -1095,14 +1136,7 @@ class DruidRewriter:
         ``__time``) or an ISO-date string dimension cast to a timestamp/date (javascript aggregator
         over the dimension: its dictionary entries as epoch ms).  The Druid output is epoch ms,
         converted back like a time column (kind "time")."""
-        e, casted = x, False
-        while True:
-            if isinstance(e, A.Cast) and e.to in ("timestamp", "date"):
-                e, casted = e.child, True
-            elif isinstance(e, A.Call) and e.name in ("datetime", "to_date", "to_timestamp") and len(e.args) == 1:
-                e, casted = e.args[0], True
-            else:
-                break
+        e, casted = _strip_time_casts(x)
         if not isinstance(e, A.Ref):
             return None
         c = pf.cols.get(e.rid)
@@ -1552,6 +1586,7 @@ class _Names:
         self.quantiles: Dict[tuple, object] = {}  # (column, interpolate) -> its one quantiles aggregator
         self.variances: Dict[tuple, object] = {}  # (column, estimator) -> its one variance aggregator
         self.comoments: Dict[tuple, object] = {}  # (column x, column y, function) -> its one aggregator
+        self.extremes: Dict[tuple, object] = {}   # (payload, ordering column, function) -> its one aggregator
 
     def agg(self) -> str:
         self.n += 1
@@ -1668,6 +1703,18 @@ def _metric_compare(c, op, value):
     if op == ">":
         return S.BoundFilterSpec(d, v, None, True, False, True)
     return S.BoundFilterSpec(d, v, None, False, False, True)
+
+
+def _strip_time_casts(x: A.Expr):
+    """(x under its casts / conversions to a timestamp or date, whether there was one)."""
+    e, casted = x, False
+    while True:
+        if isinstance(e, A.Cast) and e.to in ("timestamp", "date"):
+            e, casted = e.child, True
+        elif isinstance(e, A.Call) and e.name in ("datetime", "to_date", "to_timestamp") and len(e.args) == 1:
+            e, casted = e.args[0], True
+        else:
+            return e, casted
 
 
 def _iso_date_dictionary(ds, dim: str) -> bool:

@@ -1023,6 +1023,8 @@ def _agg_one(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, n: int, out_t:
         return _agg_quantile(call, fr, codes, ng, out_t)
     if name in A.COMOMENT_FUNCS:
         return _agg_comoment(call, fr, codes, ng, out_t)
+    if name in A.EXTREME_FUNCS:
+        return _agg_extreme(call, fr, codes, ng, out_t)
     args = [eval_series(a, fr) for a in call.args]
     x = args[0] if args else None
     if name == "count":
@@ -1090,6 +1092,20 @@ def _agg_one(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, n: int, out_t:
         r = g.agg(lambda v: list(v) if name == "collect_list" else sorted(set(v), key=str)).reindex(range(ng))
         return pd.Series(r.to_numpy(), dtype=object)
     raise AnalysisError(f"unsupported aggregate {name}")
+
+
+def _agg_extreme(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, out_t: str) -> pd.Series:
+    """max_by / min_by (x, y) per group (``ng`` = 1 without GROUP BY): x of the row at the
+    lexicographic maximum / minimum of (y, row position) over the rows whose y is non-NULL -- among
+    ties on y the last (max_by) or first (min_by) row in the table's order.  NULL for a group
+    without such a row."""
+    x, y = (eval_series(a, fr).reset_index(drop=True) for a in call.args)
+    valid = ~y.isna().to_numpy()
+    c = codes[valid] if len(codes) else np.zeros(int(valid.sum()), dtype=np.int64)
+    df = pd.DataFrame({"g": c, "y": y[valid].to_numpy(), "i": np.flatnonzero(valid)}).sort_values(["g", "y", "i"])
+    at = df.groupby("g")["i"].last() if call.name == "max_by" else df.groupby("g")["i"].first()
+    r = pd.Series(x.to_numpy(dtype=object)[at.to_numpy()], index=at.index).reindex(range(ng))
+    return to_series(r, out_t)
 
 
 def _agg_comoment(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, out_t: str) -> pd.Series:

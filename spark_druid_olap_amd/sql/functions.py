@@ -115,6 +115,17 @@ def comoment_type(call: A.Call) -> str:
     return "double"
 
 
+def extreme_type(call: A.Call) -> str:
+    """max_by / min_by (x, y): exactly two arguments, no DISTINCT; the type of x."""
+    n = call.name
+    if call.distinct:
+        raise AnalysisError(f"{n}(DISTINCT ...) is not supported")
+    if len(call.args) != 2:
+        raise AnalysisError(f"{n} takes exactly 2 arguments, got {len(call.args)}")
+    typeof(call.args[1])
+    return typeof(call.args[0])
+
+
 def agg_type(name: str, ts: Sequence[str]) -> str:
     if name == "count" or name == "approx_count_distinct":
         return "bigint"
@@ -171,7 +182,7 @@ def typeof(e: A.Expr) -> str:
         return "boolean"
     if isinstance(e, A.WindowExpr):
         f = e.func
-        if f.name in A.COMOMENT_FUNCS:
+        if f.name in A.COMOMENT_FUNCS or f.name in A.EXTREME_FUNCS:
             raise AnalysisError(f"{f.name} over a window is not supported")
         if f.name in ("rank", "dense_rank", "row_number", "ntile"):
             return "int"
@@ -185,6 +196,8 @@ def typeof(e: A.Expr) -> str:
             return quantile_type(e)
         if e.name in A.COMOMENT_FUNCS:
             return comoment_type(e)
+        if e.name in A.EXTREME_FUNCS:
+            return extreme_type(e)
         ts = [typeof(a) for a in e.args]
         if e.is_agg:
             return agg_type(e.name, ts)
