@@ -1486,7 +1486,7 @@ class PreparedEmit:
         ep.aops = [{"kind": D.A_ROWID, "col": -1, "expr": None, "filter": None, "slot": 0, "hll": -1}]
         ep.slots = [(D.S_SUM_I, 0)]
         ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
-        ep.comoments, ep.extremes = [], []
+        ep.comoments, ep.extremes, ep.histograms = [], [], []
         ep.presence_only = False
         self.prog = ep
         self.dev = prog.ds.device
@@ -1558,7 +1558,7 @@ def theta_producer_prog(prog: ScanProgram, cols: List[str]) -> ScanProgram:
                for i, c in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(cols)
     ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
-    ep.comoments, ep.extremes = [], []
+    ep.comoments, ep.extremes, ep.histograms = [], [], []
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("theta: program not eligible")
@@ -1748,7 +1748,7 @@ def quantile_producer_prog(prog: ScanProgram, cols: List[str], rowid: bool = Fal
                 for i, c in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(ep.aops)
     ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
-    ep.comoments, ep.extremes = [], []
+    ep.comoments, ep.extremes, ep.histograms = [], [], []
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("quantile: program not eligible")
@@ -2121,6 +2121,66 @@ class PreparedExtremes(_QvalRecords):
             PART_POOL.release(slab)
 
 
+FBH_TIERS = ("rep", "lds", "global")  # ops/csrc/histogram.h FbhTier
+FBH_GLOBAL_BYTES = 512 << 20         # ... FBH_GLOBAL_BYTES
+
+
+class PreparedHistogram(_QvalRecords):
+    """``fixedBucketsHistogram`` aggregators pushed into the scan: ONE producer pass writes (u32
+    group key, ordered u64 value per distinct histogram column) records, then ONE accumulation of
+    ops/csrc/histogram.hip per distinct (column, thresholds) counts them into a [G][B + 2] matrix
+    [below, c_0 .. c_{B-1}, above].  Aggregators that differ only in name or outlier mode share an
+    accumulation: the mode is applied to the matrix on the host.  Integer counts: exact and bitwise
+    reproducible.  Nothing is read back before the result copy.  G <= ``max_g``."""
+
+    def __init__(self, prog: ScanProgram, histograms: list, max_g: int):
+        from ..ops import buckets
+
+        super().__init__(prog, sorted({c for _, c, _, _ in histograms}), max_g, "histogram")
+        ds = prog.ds
+        # per distinct (column, thresholds): (value word offset, thresholds on the device, NaN bound)
+        self.passes = {}
+        self.sel = []  # per aggregator: (its pass, outlier mode)
+        for _, c, edges, mode in histograms:
+            m = ds.metrics[c]
+            thr = buckets.bucket_thresholds(edges, m.kind, int(m.scale))
+            key = (c, thr.tobytes())
+            if key not in self.passes:
+                if self.G * (len(thr) + 1) * 8 > FBH_GLOBAL_BYTES:
+                    raise RuntimeError("histogram: counters beyond the global tier's cap")
+                self.passes[key] = (self.voff(c), torch.from_numpy(thr.view(np.int64)).to(self.dev),
+                                    buckets.NAN_LO if m.kind == "double" else 0)
+            self.sel.append((key, mode))
+        self.tiers = []  # (per accumulation of the last run: its tier)
+
+    def accumulate(self, nat, st, recs: int, regions: tuple, key, tier: int = -1):
+        """One accumulation over produced records: (counts [G, B + 2] int64 on the device, tier)."""
+        voff, thr, nan_lo = self.passes[key]
+        out = torch.empty((self.G, thr.numel() + 1), dtype=torch.int64, device=self.dev)
+        tier = nat.histogram_accum(recs, self.rw, voff, *regions, thr.data_ptr(), thr.numel() - 1, nan_lo, tier,
+                                   out.data_ptr(), st)
+        return out, tier
+
+    def counts(self) -> list:
+        """Per aggregator its counts [G, B + 2] (host int64; zeros where the group holds no
+        selected row), the outlier mode applied."""
+        from ..ops import buckets
+
+        nat, st = native.load(), native._stream(self.dev)
+        pend = torch.empty(max(1, self.nch), dtype=torch.int32, device=self.dev)
+        slab = PART_POOL.acquire(self.dev, self.words)
+        try:
+            regions = self.produce(nat, st, slab, pend)
+            mats, self.tiers = {}, []
+            for key in self.passes:
+                mats[key], tier = self.accumulate(nat, st, slab.recs1.data_ptr(), regions, key)
+                self.tiers.append(FBH_TIERS[tier])
+            host = {key: m.cpu().numpy() for key, m in mats.items()}
+            return [buckets.apply_mode(host[key], mode) for key, mode in self.sel]
+        finally:
+            PART_POOL.release(slab)
+
+
 def distinct_producer_prog(prog: ScanProgram, cols: list) -> ScanProgram:
     """The scan program of a distinct producer: ``prog``'s filter, ranges and group key, one
     A_DISTINCT aggregator (the dimension's dictionary id, one record word) per (column, aggregator
@@ -2135,7 +2195,7 @@ def distinct_producer_prog(prog: ScanProgram, cols: list) -> ScanProgram:
                 "filt_off": off, "filt_len": n} for i, (c, (off, n)) in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(cols)
     ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
-    ep.comoments, ep.extremes = [], []
+    ep.comoments, ep.extremes, ep.histograms = [], [], []
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("distinct: program not eligible")

@@ -218,6 +218,9 @@ class PreparedQuery:
             self._full_prog = prog
             if prog.quantiles:
                 _check_quantile_refs(qs, {name for name, _, _, _ in prog.quantiles})
+            if prog.histograms:
+                _check_quantile_refs(qs, {name for name, _, _, _ in prog.histograms}, "fixedBucketsHistogram",
+                                     "count per bucket")
             # grouped on the shard key across several ranks: scan this shard's key window only
             self.window = shard_window(prog, ds, self.world)
             if self.window is not None:
@@ -502,7 +505,10 @@ class PreparedQuery:
                 self._moments(self._full_prog, cols)
                 co_tiers = self._comoments(self._full_prog, cols)
                 ext_tiers = self._extremes(self._full_prog, cols)
+                hist_tiers = self._histograms(self._full_prog, cols)
                 res = self._post(prog, cols)
+                if hist_tiers:
+                    res.stats["histogram_device"] = hist_tiers
                 if tiers:
                     res.stats["distinct_count_device"] = tiers
                 if co_tiers:
@@ -1409,6 +1415,65 @@ class PreparedQuery:
             return None
         return ep.values()
 
+    # ------------------------------------------------------------------ fixed-bucket histograms
+    def _histograms(self, prog: ScanProgram, cols: Dict[str, np.ndarray]) -> Optional[list]:
+        """``fixedBucketsHistogram`` aggregators: per group the int64 counts [below, c_0 .. c_{B-1},
+        above] of the selected rows' values, a result column [groups, B + 2] like a quantiles
+        column.  On the native GPU engine the HIP bucket counts answer (engine/device_exec.py
+        PreparedHistogram); everywhere else -- CPU, the reference executor, hashed keys, more than
+        QUANTILE_SELECT_MAX_G groups -- torch counts against the same thresholds (ops/reference.py
+        group_histogram): both are exact.  Returns the tier per accumulation when the device
+        answered (the result's ``histogram_device`` stats entry), else None."""
+        if not prog.histograms:
+            return None
+        gid_order = np.asarray(cols["__gid__"], dtype=np.int64)
+        fused = self._histograms_fused(prog)
+        if fused is not None:
+            for (name, _, _, _), res in zip(prog.histograms, fused):
+                cols[name] = res[np.clip(gid_order, 0, max(0, len(res) - 1))]
+            return list(self._histogram_prep.tiers)
+        from ..ops import buckets
+        from ..ops.reference import _rows, compute_keys, eval_bexpr, group_histogram
+        from .lower import column_tensor
+
+        ds = self.ds
+        rows = _rows(prog) if not prog.empty else torch.zeros(0, dtype=torch.int64, device=ds.device)
+        if rows.numel():
+            rows = rows[eval_bexpr(prog, prog.bexpr, rows)]
+        keys = compute_keys(prog, rows)
+        mats = {}  # (column, thresholds) -> (group keys, counts)
+        for name, c, edges, mode in prog.histograms:
+            m = ds.metrics[c]
+            thr = buckets.bucket_thresholds(edges, m.kind, int(m.scale))
+            if (c, thr.tobytes()) not in mats:
+                gids, cnt = group_histogram(keys, column_tensor(ds, c)[rows], thr)
+                mats[(c, thr.tobytes())] = (gids.cpu().numpy(), cnt.cpu().numpy())
+            gids, cnt = mats[(c, thr.tobytes())]
+            pos = np.clip(np.searchsorted(gids, gid_order), 0, max(0, len(gids) - 1))
+            hit = gids[pos] == gid_order if len(gids) else np.zeros(len(gid_order), dtype=bool)
+            cols[name] = buckets.apply_mode(np.where(hit[:, None], cnt[pos], 0), mode) if len(gids) else \
+                np.zeros((len(gid_order), len(thr) + 1), dtype=np.int64)
+        return None
+
+    def _histograms_fused(self, prog: ScanProgram) -> Optional[list]:
+        """Per fixedBucketsHistogram aggregator its counts [G, B + 2] from the device, or None where
+        it does not apply (CPU, hashed or ineligible keys, too many groups or counters, an empty
+        shard)."""
+        if prog.empty or self.ds.device.type != "cuda" or not self.engine.use_native:
+            return None
+        ep = self.__dict__.get("_histogram_prep")
+        if ep is None:
+            try:
+                from .device_exec import PreparedHistogram
+
+                ep = PreparedHistogram(prog, prog.histograms, QUANTILE_SELECT_MAX_G)
+            except RuntimeError:
+                ep = False
+            self._histogram_prep = ep
+        if ep is False:
+            return None
+        return ep.counts()
+
     # ------------------------------------------------------------------ post processing
     def _post(self, prog: ScanProgram, cols: Dict[str, np.ndarray]) -> QueryResult:
         qs = self.qs
@@ -1775,15 +1840,16 @@ THETA_SELECT_MAX_G = 4096  # groups the device radix select handles (histogram G
 QUANTILE_SELECT_MAX_G = 1 << 16  # groups the device rank select handles (state rows G x targets)
 
 
-def _check_quantile_refs(qs, names) -> None:
-    """A quantiles column holds one value per fraction: HAVING, limitSpec ordering, a topN metric or
-    a post-aggregation cannot read it as a number (SQL projects the fractions out first)."""
+def _check_quantile_refs(qs, names, what: str = "quantiles", per: str = "value per fraction") -> None:
+    """A quantiles column holds one value per fraction (a fixedBucketsHistogram column one count per
+    bucket): HAVING, limitSpec ordering, a topN metric or a post-aggregation cannot read it as a
+    number (SQL projects the fractions out first)."""
     import dataclasses
 
     def walk(x):
         if isinstance(x, str):
             if x in names:
-                raise LoweringError(f"the quantiles aggregator {x!r} holds one value per fraction: it cannot be "
+                raise LoweringError(f"the {what} aggregator {x!r} holds one {per}: it cannot be "
                                     "read by having / limitSpec / metric / postAggregations")
         elif isinstance(x, (list, tuple)):
             for y in x:

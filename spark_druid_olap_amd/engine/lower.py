@@ -376,6 +376,8 @@ class ScanProgram:
     comoments: List[Tuple[str, str, str, str]] = field(default_factory=list)
     # max_by / min_by: (name, payload metric, ordering metric or "__time", is max)
     extremes: List[Tuple[str, str, str, bool]] = field(default_factory=list)
+    # fixed-bucket histograms: (name, metric, edges as Fractions, outlier mode)
+    histograms: List[Tuple[str, str, tuple, str]] = field(default_factory=list)
     luts: Dict[str, torch.Tensor] = field(default_factory=dict)       # dim -> f64 value per dictionary id
     lut_ptrs: Dict[float, torch.Tensor] = field(default_factory=dict)  # E_LUT operand -> its table
     # grouping keys functionally determined by a packed key: (key, index of determinant in keys,
@@ -394,11 +396,12 @@ class ScanProgram:
     @property
     def needs_rows(self) -> bool:
         """Some aggregator reads the selected rows themselves (theta KMV, order statistics, exact
-        distinct counts, variances, covariances, values at an extreme), not an accumulator: strategies
-        that keep only accumulators decline, the executor answers it after the scan
-        (engine/executor.py _theta / _quantile / _distinct / _moments / _comoments / _extremes)."""
+        distinct counts, variances, covariances, values at an extreme, bucket counts), not an
+        accumulator: strategies that keep only accumulators decline, the executor answers it after the
+        scan (engine/executor.py _theta / _quantile / _distinct / _moments / _comoments / _extremes /
+        _histograms)."""
         return bool(self.thetas or self.quantiles or self.distincts or self.moments or self.comoments or
-                    self.extremes)
+                    self.extremes or self.histograms)
 
     @property
     def nhll_total(self) -> int:
@@ -1431,6 +1434,31 @@ class Lowerer:
             prog.extremes.append((a.name, a.fieldName, a.byFieldName, isinstance(a, S.MaxByAggregationSpec)))
             prog.aggs.append(AggOut(a.name, "moment", combine="moment",
                                     out_type="long" if ds.metrics[a.fieldName].kind == "long" else "double"))
+            return
+        if isinstance(a, S.FixedBucketsHistogramAggregationSpec):
+            from ..ops import buckets
+
+            what = a.type
+            if self.world is not None and self.world.distributed:
+                # (the counts are additive, but they are not reduced across ranks yet)
+                raise LoweringError(f"{what} aggregators are not answered across ranks")
+            m = ds.metrics.get(a.fieldName)
+            if m is None:
+                raise LoweringError(f"{what} over {a.fieldName!r}: not a metric")
+            if m.sketch is not None or m.kind not in ("long", "double", "decimal"):
+                raise LoweringError(f"{what} over the sketch metric {a.fieldName!r}")
+            if a.outlierHandlingMode not in buckets.MODES:
+                raise LoweringError(f"{what}: unsupported outlierHandlingMode {a.outlierHandlingMode!r}")
+            if filt is not None:
+                raise LoweringError(f"{what} inside a filtered aggregator is not supported")
+            try:
+                edges = buckets.bucket_edges(a.lowerLimit, a.upperLimit, a.numBuckets, a.breaks)
+                buckets.bucket_thresholds(edges, m.kind, int(m.scale))
+            except ValueError as e:
+                raise LoweringError(f"{what}: {e}") from None
+            # (integer counts: exact and bitwise reproducible, so allowed in deterministic mode)
+            prog.histograms.append((a.name, a.fieldName, tuple(edges), a.outlierHandlingMode))
+            prog.aggs.append(AggOut(a.name, "quantile", combine="quantile"))
             return
         raise LoweringError(f"unsupported aggregator {type(a).__name__}")
 

@@ -27,6 +27,7 @@
 #include "moments.h"
 #include "comoments.h"
 #include "extreme.h"
+#include "histogram.h"
 
 namespace sdo {
 template <int U>
@@ -176,6 +177,19 @@ __global__ void ext_global_regions_kernel(const uint32_t* __restrict__ recs, int
                                           uint64_t* __restrict__ state);
 __global__ void ext_init_kernel(uint64_t* state, int64_t n, int dirs);
 __global__ void ext_final_kernel(ExtFinalArgs a);
+// histogram.hip (shapes: histogram.h)
+__global__ void fbh_rep_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff,
+                                       const uint32_t* __restrict__ seg_lo, const uint32_t* __restrict__ seg_hi,
+                                       int64_t nseg, const uint64_t* __restrict__ thr, uint32_t T, uint64_t nan_lo,
+                                       uint32_t G, uint32_t R, uint64_t* __restrict__ out);
+__global__ void fbh_lds_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff,
+                                       const uint32_t* __restrict__ seg_lo, const uint32_t* __restrict__ seg_hi,
+                                       int64_t nseg, const uint64_t* __restrict__ thr, uint32_t T, uint64_t nan_lo,
+                                       uint32_t g0, uint32_t GL, uint64_t* __restrict__ out);
+__global__ void fbh_global_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff,
+                                          const uint32_t* __restrict__ seg_lo, const uint32_t* __restrict__ seg_hi,
+                                          int64_t nseg, const uint64_t* __restrict__ thr, uint32_t T, uint64_t nan_lo,
+                                          uint32_t G, uint64_t* __restrict__ out);
 // p2p.hip (P2PArgs: p2p.h)
 __global__ void p2p_merge_kernel(P2PArgs a);
 }  // namespace sdo
@@ -1336,6 +1350,63 @@ static void extreme_final(std::vector<ExtTuple> payloads, int64_t G, int64_t row
 }
 
 // ---------------------------------------------------------------------------------------------
+// Fixed-bucket histograms: per-group bucket counts over (key, ordered values ...) records
+// (histogram.hip).  `thr`: B + 1 ascending u64 thresholds in the records' ordered domain (device),
+// `nan_lo`: ordered values below it are NaNs and count as "above" (0 for integer columns).  Counts
+// the records into the [G][B + 2] u64 `out`, which is cleared first.  `tier` -1 picks the tier from
+// the counter space (histogram.h fbh_tier); 0..2 asks for one that can hold it.  Returns the tier used.
+static int histogram_accum(uint64_t recs, int rw, int voff, uint64_t seg_lo, uint64_t seg_hi, int64_t nseg, int64_t G,
+                           uint64_t thr, int64_t B, uint64_t nan_lo, int tier, uint64_t out, uint64_t stream) {
+  qsel_check(rw, voff, G);
+  if (!sdo::fbh_buckets_ok(B)) throw std::invalid_argument("histogram_accum: 1..1022 buckets");
+  if (nseg < 0 || !thr || !out) throw std::invalid_argument("histogram_accum: arguments");
+  const int S = (int)B + 2;
+  const uint32_t T = (uint32_t)B + 1;
+  if (G * S * 8 > sdo::FBH_GLOBAL_BYTES) throw std::invalid_argument("histogram_accum: counters beyond 512 MiB");
+  if (tier < 0) tier = sdo::fbh_tier(G, S);
+  if (tier > sdo::FBH_TIER_GLOBAL || !sdo::fbh_tier_holds(tier, G, S))
+    throw std::invalid_argument("histogram_accum: tier does not hold G");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(sdo::qsel_clear_kernel, dim3(grid_for(G * S * 2, 256, 4096)), dim3(256), 0, s, (uint32_t*)out,
+                     G * S * 2);
+  check(hipGetLastError(), "histogram clear launch");
+  if (nseg == 0) return tier;
+  // (the grids of moments_accum: rep / lds workgroups end with a flush onto the same global words)
+  const unsigned grid = (unsigned)std::min<int64_t>(nseg, tier == sdo::FBH_TIER_GLOBAL ? 4096 : 1024);
+  const uint32_t* r = (const uint32_t*)recs;
+  const uint32_t *lo = (const uint32_t*)seg_lo, *hi = (const uint32_t*)seg_hi;
+  const uint64_t* th = (const uint64_t*)thr;
+  uint64_t* o = (uint64_t*)out;
+  // dynamic LDS: the thresholds, then the u32 counters; beyond 64 KiB a kernel has to be told once
+  auto lds_for = [&](const void* fn, int64_t counters) {
+    const size_t lds = (size_t)T * 8 + (size_t)counters * 4;
+    if (lds > 64 * 1024)
+      check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "histogram LDS attribute");
+    return lds;
+  };
+  if (tier == sdo::FBH_TIER_REP) {
+    int R = 64;  // (fbh_rep, or a single copy where a forced tier holds more than FBH_REP_COUNTERS)
+    while (R > 1 && G * S * R > sdo::FBH_LDS_COUNTERS) R >>= 1;
+    const size_t lds = lds_for((const void*)sdo::fbh_rep_regions_kernel, G * S * R);
+    hipLaunchKernelGGL(sdo::fbh_rep_regions_kernel, dim3(grid), dim3(256), lds, s, r, rw, voff, lo, hi, nseg, th, T,
+                       nan_lo, (uint32_t)G, (uint32_t)R, o);
+  } else if (tier == sdo::FBH_TIER_LDS) {
+    // one pass per key slice of (nearly) equal size, each table within the LDS budget
+    const uint32_t cap = (uint32_t)sdo::fbh_lds_groups(S), Gu = (uint32_t)G;
+    const uint32_t slices = (Gu + cap - 1) / cap, GL = (Gu + slices - 1) / slices;
+    const size_t lds = lds_for((const void*)sdo::fbh_lds_regions_kernel, (int64_t)GL * S);
+    for (uint32_t g0 = 0; g0 < Gu; g0 += GL)
+      hipLaunchKernelGGL(sdo::fbh_lds_regions_kernel, dim3(grid), dim3(256), lds, s, r, rw, voff, lo, hi, nseg, th, T,
+                         nan_lo, g0, std::min(GL, Gu - g0), o);
+  } else {
+    hipLaunchKernelGGL(sdo::fbh_global_regions_kernel, dim3(grid), dim3(256), (size_t)T * 8, s, r, rw, voff, lo, hi,
+                       nseg, th, T, nan_lo, (uint32_t)G, o);
+  }
+  check(hipGetLastError(), "histogram accumulation launch");
+  return tier;
+}
+
+// ---------------------------------------------------------------------------------------------
 // LIKE / contains / fragment over a dictionary's device text heap (dict_match.hip): bit e of `out`
 // says entry e matches `program` (a packed DmProgram); when the program folds case, bit e of
 // `nonascii` says entry e holds a byte >= 0x80 (the host re-evaluates those).  `heap` is 16-byte
@@ -1644,6 +1715,7 @@ PYBIND11_MODULE(_sdo_native, m) {
   m.def("comoments_final", &comoments_final);
   m.def("extreme_accum", &extreme_accum);
   m.def("extreme_final", &extreme_final);
+  m.def("histogram_accum", &histogram_accum);
   m.def("dict_match", &dict_match);
   m.def("dict_match_layout", &dict_match_layout);
   m.def("part_agg", &part_agg);

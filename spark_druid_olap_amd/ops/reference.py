@@ -474,6 +474,26 @@ def group_extremes(keys: torch.Tensor, y: torch.Tensor, rows: torch.Tensor, is_m
         0, inv[tied], rows[tied], how, include_self=False)
 
 
+def group_histogram(keys: torch.Tensor, v: torch.Tensor, thresholds: np.ndarray):
+    """Fixed-bucket counts by group: (group keys ascending, counts [groups, B + 2] int64) of the
+    (group key, stored value v) pairs against the B + 1 ordered-u64 ``thresholds`` of ops/buckets.py
+    -- a value's slot is the number of thresholds <= it, NaNs take the last.  Exact, as
+    ops/csrc/histogram.hip: the engine's answer wherever that does not apply."""
+    S = len(thresholds) + 1
+    gids, inv = torch.unique(keys.to(torch.int64), return_inverse=True)
+    # (the u64 order with the sign bit flipped back is int64 order: integers as stored, doubles as f2ord)
+    thr = torch.from_numpy((thresholds ^ np.uint64(1 << 63)).view(np.int64)).to(v.device)
+    if v.dtype.is_floating_point:
+        f = v.to(torch.float64)
+        b = f.view(torch.int64)
+        s = torch.where(b >= 0, b, b ^ 0x7FFFFFFFFFFFFFFF)
+        slot = torch.where(torch.isnan(f), S - 1, torch.searchsorted(thr, s, right=True))
+    else:
+        slot = torch.searchsorted(thr, v.to(torch.int64), right=True)
+    flat = torch.bincount(inv * S + slot, minlength=len(gids) * S)
+    return gids, flat.view(len(gids), S)
+
+
 def run_reference_mask(prog) -> torch.Tensor:
     """Row ids passing the filter (select queries)."""
     dev = prog.ds.device

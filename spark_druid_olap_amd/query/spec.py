@@ -591,6 +591,28 @@ class MinByAggregationSpec(_ExtremeBySpec):
     type: str = "minBy"
 
 
+@_register("aggregation", "fixedBucketsHistogram")
+@dataclass
+class FixedBucketsHistogramAggregationSpec(Spec, _Decodable):
+    """Counts of the selected rows' ``fieldName`` (a long / decimal / double metric) in
+    ``numBuckets`` equal buckets over [``lowerLimit``, ``upperLimit``) -- the aggregator of Druid's
+    histogram extension -- or, this project's own, in the buckets between the strictly ascending
+    ``breaks``, used instead of the three limits when present.  Limits and breaks are read as the
+    exact decimal value of their shortest text (0.1 is 1/10); a value v is in bucket i iff
+    e_i <= v < e_{i+1}.  The result is one array of numBuckets + 2 longs per group: [below,
+    c_0 .. c_{B-1}, above]; NaN counts as above.  ``outlierHandlingMode``: ``"ignore"`` reports the
+    array as is, ``"overflow"`` adds below into c_0 and above into c_{B-1} and reports 0 at the two
+    ends (``"clip"`` is not supported)."""
+    name: str
+    fieldName: str
+    numBuckets: Optional[int] = None
+    lowerLimit: Optional[float] = None
+    upperLimit: Optional[float] = None
+    outlierHandlingMode: str = "ignore"
+    breaks: Optional[List[float]] = None
+    type: str = "fixedBucketsHistogram"
+
+
 # ============================================================================ post aggregations
 @_register("postagg", "fieldAccess")
 @dataclass

@@ -143,13 +143,16 @@ class Alias(Expr):
 AGG_FUNCS = {"count", "sum", "min", "max", "avg", "mean", "approx_count_distinct", "first", "last",
              "stddev", "stddev_samp", "stddev_pop", "variance", "var_samp", "var_pop", "collect_set",
              "collect_list", "grouping", "grouping_id", "percentile", "median", "percentile_approx",
-             "approx_percentile", "corr", "covar_samp", "covar_pop", "max_by", "min_by"}
+             "approx_percentile", "corr", "covar_samp", "covar_pop", "max_by", "min_by",
+             "histogram"}
 # exact order statistics (query/spec.py QuantilesAggregationSpec)
 QUANTILE_FUNCS = {"percentile", "median", "percentile_approx", "approx_percentile"}
 # two-column statistics (query/spec.py CovarianceAggregationSpec / CorrelationAggregationSpec)
 COMOMENT_FUNCS = {"corr", "covar_samp", "covar_pop"}
 # the value at an extreme (query/spec.py MaxByAggregationSpec / MinByAggregationSpec)
 EXTREME_FUNCS = {"max_by", "min_by"}
+# fixed-bucket counts (query/spec.py FixedBucketsHistogramAggregationSpec)
+HISTOGRAM_FUNCS = {"histogram"}
 
 
 @dataclass(frozen=True, repr=False)

@@ -33,7 +33,8 @@ from ..query import transforms as QT
 from ..query.intervals import fmt_iso
 from . import ast as A
 from . import plan as P
-from .functions import Frame, Period, constant_fold, evaluate, is_deterministic, quantile_args, typeof
+from .functions import (Frame, Period, constant_fold, evaluate, histogram_args, is_deterministic, quantile_args,
+                        typeof)
 from .jscodegen import JSGenError, js_aggregator, js_expr, js_single_column_fn, vm_compatible
 from .types import AnalysisError, INTEGRAL, base, is_vec, to_series
 
@@ -700,7 +701,8 @@ class DruidRewriter:
                 r = A.Ref(A.new_id(), spec_.name, t)
                 if isinstance(spec_, (S.QuantilesAggregationSpec, S.VarianceAggregationSpec,
                                       S.CovarianceAggregationSpec, S.CorrelationAggregationSpec,
-                                      S.MaxByAggregationSpec, S.MinByAggregationSpec)):
+                                      S.MaxByAggregationSpec, S.MinByAggregationSpec,
+                                      S.FixedBucketsHistogramAggregationSpec)):
                     shared[id(spec_)] = r
                 drefs.append(r)
                 columns.append((spec_.name, t, part[2] if len(part) > 2 else "value"))
@@ -960,6 +962,8 @@ class DruidRewriter:
             return self._comoment_agg(pf, call, names, rolled)
         if n in A.EXTREME_FUNCS:
             return self._extreme_agg(pf, call, names, rolled)
+        if n in A.HISTOGRAM_FUNCS:
+            return self._histogram_agg(pf, call, names, rolled)
         raise NotPushable(f"aggregate {n} is not pushable")
 
     def _comoment_agg(self, pf: PF, call: A.Call, names: "_Names", rolled: bool):
@@ -1031,6 +1035,32 @@ class DruidRewriter:
         xt = typeof(x)
         long_ = pf.table.info.datasource.metrics[fields[0]].kind == "long" and base(xt) in INTEGRAL
         return [(spec, xt if long_ else "double")], lambda rs: rs[0]  # (cast to x's type by the caller)
+
+    def _histogram_agg(self, pf: PF, call: A.Call, names: "_Names", rolled: bool):
+        """histogram(x, lo, hi, n) / histogram(x, array(b0, ..., bB)) over a plain long / decimal /
+        double metric -> ONE ``fixedBucketsHistogram`` aggregator per (column, limits) of the query,
+        whose array column is the result.  The counts are per shard: a distributed session answers
+        on the host."""
+        histogram_args(call)
+        if rolled or getattr(pf.table.info.datasource, "rollup", False):
+            raise NotPushable("histogram over a rolled-up datasource")
+        if self.session.engine.world.distributed:
+            raise NotPushable("histogram across ranks")
+        x = call.args[0]
+        if not isinstance(x, A.Ref):
+            raise NotPushable("histogram over an expression")
+        c = self._column(pf, x)
+        m = pf.table.info.datasource.metrics.get(c.druid_column) if c.is_metric else None
+        if m is None or m.sketch is not None or m.kind not in ("long", "decimal", "double"):
+            raise NotPushable(f"histogram over {c.column}: not a long / decimal / double metric")
+        lims = [a.value for a in (call.args[1].args if len(call.args) == 2 else call.args[1:])]
+        key = (c.druid_column, len(call.args), tuple(lims))
+        spec = names.histograms.get(key)
+        if spec is None:
+            spec = names.histograms[key] = \
+                S.FixedBucketsHistogramAggregationSpec(names.agg(), c.druid_column, breaks=lims) if len(call.args) == 2 \
+                else S.FixedBucketsHistogramAggregationSpec(names.agg(), c.druid_column, lims[2], lims[0], lims[1])
+        return [(spec, "array", "histogram")], lambda rs: rs[0]
 
     def _variance_agg(self, pf: PF, call: A.Call, names: "_Names", rolled: bool):
         """stddev / stddev_samp / stddev_pop / variance / var_samp / var_pop over a plain long /
@@ -1587,6 +1617,7 @@ class _Names:
         self.variances: Dict[tuple, object] = {}  # (column, estimator) -> its one variance aggregator
         self.comoments: Dict[tuple, object] = {}  # (column x, column y, function) -> its one aggregator
         self.extremes: Dict[tuple, object] = {}   # (payload, ordering column, function) -> its one aggregator
+        self.histograms: Dict[tuple, object] = {}  # (column, form, limits) -> its one aggregator
 
     def agg(self) -> str:
         self.n += 1

@@ -18,7 +18,7 @@ import pandas as pd
 from ..query import spec as S
 from . import ast as A
 from . import plan as P
-from .functions import Frame, eval_series, evaluate, quantile_args, typeof
+from .functions import Frame, eval_series, evaluate, histogram_args, quantile_args, typeof
 from .types import AnalysisError, INTEGRAL, base, broadcast, fast_series, is_vec, pandas_dtype, to_series
 
 
@@ -798,6 +798,8 @@ def druid_value_lazy(col, sqlt: str, kind: str, n: int):
     if type(col) is _DictColumn:
         return LazySeries(None, None, (col, sqlt))
     if getattr(col, "ndim", 1) == 2:  # a quantiles aggregator: one array of values per group
+        if sqlt == "array" and kind == "histogram":  # (bucket counts: one Python list per group, as the host aggregate's)
+            return pd.Series(np.asarray(col).tolist(), dtype=object)
         return pd.Series(list(col), dtype=object)
     if kind != "time":
         if type(col) is np.ndarray:
@@ -1025,7 +1027,9 @@ def _agg_one(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, n: int, out_t:
         return _agg_comoment(call, fr, codes, ng, out_t)
     if name in A.EXTREME_FUNCS:
         return _agg_extreme(call, fr, codes, ng, out_t)
-    args = [eval_series(a, fr) for a in call.args]
+    if name in A.HISTOGRAM_FUNCS:
+        return _agg_histogram(call, fr, codes, ng)
+    args =[eval_series(a, fr) for a in call.args]
     x = args[0] if args else None
     if name == "count":
         valid = np.ones(n, dtype=bool)
@@ -1092,6 +1096,29 @@ def _agg_one(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, n: int, out_t:
         r = g.agg(lambda v: list(v) if name == "collect_list" else sorted(set(v), key=str)).reindex(range(ng))
         return pd.Series(r.to_numpy(), dtype=object)
     raise AnalysisError(f"unsupported aggregate {name}")
+
+
+def _agg_histogram(call: A.Call, fr: Frame, codes: np.ndarray, ng: int) -> pd.Series:
+    """histogram(x, ...) per group (``ng`` = 1 without GROUP BY): the counts [below, c_0 .. c_{B-1},
+    above] of the non-NULL x against the exact edges, binned by the thresholds the pushed aggregator
+    uses (ops/buckets.py) -- integral x as a long column, everything else as a double one.  NULL for
+    a group without such a row."""
+    from ..ops import buckets
+
+    edges = histogram_args(call)
+    x = eval_series(call.args[0], fr).reset_index(drop=True)
+    valid = ~x.isna().to_numpy()
+    kind = "long" if base(typeof(call.args[0])) in INTEGRAL else "double"
+    xv = x[valid].to_numpy(dtype=np.int64) if kind == "long" else x[valid].astype("float64").to_numpy(dtype=np.float64)
+    S_ = len(edges) + 1
+    c = codes[valid] if len(codes) else np.zeros(len(xv), dtype=np.int64)
+    slot = buckets.slots(xv, buckets.bucket_thresholds(edges, kind), kind)
+    cnt = np.bincount(c * S_ + slot, minlength=ng * S_).reshape(ng, S_).astype(np.int64)
+    full = np.empty(ng, dtype=object)
+    full[:] = None
+    for i in np.flatnonzero(cnt.sum(axis=1) > 0):
+        full[i] = cnt[i].tolist()
+    return pd.Series(full, dtype=object)
 
 
 def _agg_extreme(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, out_t: str) -> pd.Series:

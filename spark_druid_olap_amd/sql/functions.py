@@ -126,6 +126,39 @@ def extreme_type(call: A.Call) -> str:
     return typeof(call.args[0])
 
 
+def histogram_args(call: A.Call) -> list:
+    """The exact bucket edges (ops/buckets.py) of ``histogram(x, lo, hi, n)`` -- n equal buckets over
+    [lo, hi) -- or ``histogram(x, array(b0, ..., bB))``: the limits are numeric literals, n a
+    positive integer literal, lo < hi, the breaks at least two and strictly ascending."""
+    from ..ops import buckets
+
+    if call.distinct:
+        raise AnalysisError("histogram(DISTINCT ...) is not supported")
+    rest = call.args[1:]
+    is_arr = len(rest) == 1 and isinstance(rest[0], A.Call) and rest[0].name == "array"
+    if not is_arr and len(rest) != 3:
+        raise AnalysisError("histogram takes (x, lo, hi, n) or (x, array(b0, ..., bB))")
+    vals = []
+    for x in (rest[0].args if is_arr else rest):
+        v = x.value if isinstance(x, A.Lit) else None
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise AnalysisError(f"histogram: the limits must be numeric literals, got {x.sql()}")
+        vals.append(v)
+    try:
+        return buckets.bucket_edges(breaks=vals) if is_arr else buckets.bucket_edges(*vals)
+    except ValueError as e:
+        raise AnalysisError(str(e)) from None
+
+
+def histogram_type(call: A.Call) -> str:
+    """histogram(x, ...): an array of B + 2 bigint counts [below, c_0 .. c_{B-1}, above]."""
+    histogram_args(call)
+    t = typeof(call.args[0])
+    if base(t) not in INTEGRAL and base(t) not in ("double", "float", "decimal"):
+        raise AnalysisError(f"histogram over the non-numeric type {t}")
+    return "array"
+
+
 def agg_type(name: str, ts: Sequence[str]) -> str:
     if name == "count" or name == "approx_count_distinct":
         return "bigint"
@@ -182,7 +215,7 @@ def typeof(e: A.Expr) -> str:
         return "boolean"
     if isinstance(e, A.WindowExpr):
         f = e.func
-        if f.name in A.COMOMENT_FUNCS or f.name in A.EXTREME_FUNCS:
+        if f.name in A.COMOMENT_FUNCS or f.name in A.EXTREME_FUNCS or f.name in A.HISTOGRAM_FUNCS:
             raise AnalysisError(f"{f.name} over a window is not supported")
         if f.name in ("rank", "dense_rank", "row_number", "ntile"):
             return "int"
@@ -198,6 +231,8 @@ def typeof(e: A.Expr) -> str:
             return comoment_type(e)
         if e.name in A.EXTREME_FUNCS:
             return extreme_type(e)
+        if e.name in A.HISTOGRAM_FUNCS:
+            return histogram_type(e)
         ts = [typeof(a) for a in e.args]
         if e.is_agg:
             return agg_type(e.name, ts)
