@@ -25,7 +25,8 @@ import torch
 from ..ops import desc as D
 from ..ops import native
 from .lower import ScanProgram, distinct_null_id, pack
-from .partials import Partials
+from . import partials as _partials
+from .partials import DeferredSparse, Partials
 from .scheduler import current_slot
 
 from ..planner.cost import PLAN_LDS_BUDGET as LDS_BUDGET  # noqa: E402  (single source: the cost model)
@@ -456,7 +457,10 @@ class PreparedScan:
             b.arena = (gen, off, ep)
             if not intact:
                 b.clean = False  # another scan wrote over the region: the next launch resets it
+                _settle_pending(b, False)
             return b
+        if b is not None:
+            _settle_pending(b, False)
         v = _Bufs()
         v.geom = self._geom(cap)
         v.hll, v.hll32 = [], []
@@ -509,7 +513,7 @@ class PreparedScan:
         b.rows = rows
         b.geom = self._geom(cap)
         b.init_row = _init_row(dev, tuple(int(init) for _, init in prog.slots))
-        b.arena = None
+        b.arena = b.pending = None
         if reuse is not None and getattr(reuse, "geom", None) == b.geom:
             b.acc, b.keys, b.hll, b.hll32 = reuse.acc, reuse.keys, reuse.hll, reuse.hll32
             b.overflow, b.touch = reuse.overflow, reuse.touch
@@ -871,6 +875,8 @@ class PreparedScan:
         self._maybe_specialize()
         prog = self.prog
         b = self._bufs()
+        if b.pending is not None:
+            _settle_pending(b, True)
         if prog.empty:
             if self.mode != D.M_HASH:
                 # dense layout even when this shard has nothing to scan: every rank must issue the
@@ -895,10 +901,14 @@ class PreparedScan:
             for h8, h32 in zip(b.hll, b.hll32):  # scan-time u32 registers -> the byte registers
                 h8.copy_(h32)
             if self.touch:
-                # touched groups' ids and rows, re-initialised in the same pass (post_scan.hip touch_*)
-                idx, acc = native.touch_compact(b.touch, b.acc, b.init_row)
-                b.clean = True
-                return Partials("sparse", acc, idx, [])
+                # the touched groups are counted here and leave the table -- re-initialised in the
+                # same pass (post_scan.hip touch_*) -- when the state is read: as final columns
+                # (finalize) or as ids and rows (every other consumer)
+                sp = DeferredSparse(native.touch_count(b.touch, b.acc, b.init_row), b)
+                b.pending = weakref.ref(sp)
+                if not _partials.FUSED_TOUCH_DECODE:
+                    sp.gather()
+                return sp
             if self.pres_bytes:
                 idx = native.nonzero_rows(b.acc)
                 return Partials("sparse", torch.ones((idx.numel(), 1), dtype=torch.int64, device=self.dev), idx, [])
@@ -1236,7 +1246,22 @@ def _settle_forgotten() -> None:
 class _Bufs:
     """One execution slot's device buffers for a prepared scan."""
     __slots__ = ("cap", "rows", "init_row", "acc", "keys", "hll", "hll32", "overflow", "desc", "touch", "clean",
-                 "run_args", "noreset_args", "part", "geom", "arena", "__weakref__")
+                 "run_args", "noreset_args", "part", "geom", "arena", "pending", "__weakref__")
+
+
+def _settle_pending(b: "_Bufs", rerun: bool) -> None:
+    """A deferred first-touch state (engine/partials.py DeferredSparse) still lying in ``b``'s tables
+    when they are about to be written again.  ``rerun`` (the same scan runs again on these buffers):
+    a state somebody still holds is gathered now and stays valid; a dropped one leaves its marks and
+    rows behind, ``b.clean`` is still False and the launch resets the whole table.  Otherwise (the
+    arena region was carved over or handed on) a held state can only be refused when it is read."""
+    ref, b.pending = b.pending, None
+    p = ref() if ref is not None else None
+    if p is not None and p.pending:
+        if rerun:
+            p.gather()
+        else:
+            p.lost = True
 
 
 # Slot arenas.  A BI dashboard sends many statement shapes and parameterizations; caching one set of

@@ -52,6 +52,64 @@ class Partials:
                         self.scattered, self.status)
 
 
+class DeferredSparse(Partials):
+    """Sparse partials of a first-touch scan (engine/device_exec.py) whose groups are counted but
+    still lie in the scan's accumulator table: ``finalize`` turns them into host columns in one
+    kernel (``_native_sparse``: post_scan.hip touch_decode_kernel); any other consumer reads
+    ``keys`` / ``acc``, which gathers them first (ops/native.py touch_gather) -- from then on this is
+    an ordinary sparse state.  Either way the table's touched rows are re-initialised and the slot's
+    buffers marked clean (``bufs``: the scan's _Bufs, whose ``pending`` names this state meanwhile)."""
+
+    def __init__(self, count, bufs):
+        Partials.__init__(self, "sparse", None, None)
+        self.count, self.bufs, self.lost, self.n = count, bufs, False, count.n
+
+    @property
+    def pending(self) -> bool:
+        return self.count is not None
+
+    def take(self):
+        """The counted table (ops/native.py TouchCount) for whoever empties it now."""
+        if self.lost:
+            raise RuntimeError("deferred sparse partials read after their scan's buffers were re-used")
+        c, b = self.count, self.bufs
+        self.count = self.bufs = None
+        b.clean, b.pending = True, None
+        return c
+
+    def gather(self) -> None:
+        """Materialise ``keys`` / ``acc`` (no-op once done)."""
+        if self.pending:
+            from ..ops import native
+
+            self._keys, self._acc = native.touch_gather(self.take())
+
+    def __repr__(self) -> str:  # (the dataclass's would read -- and so gather -- keys / acc)
+        return f"DeferredSparse(rows={self.rows}, pending={self.pending})"
+
+    @property
+    def rows(self) -> int:
+        return self.n if self._acc is None else int(self._acc.shape[0])
+
+    @property
+    def keys(self):
+        self.gather()
+        return self._keys
+
+    @keys.setter
+    def keys(self, v):
+        self._keys = v
+
+    @property
+    def acc(self):
+        self.gather()
+        return self._acc
+
+    @acc.setter
+    def acc(self, v):
+        self._acc = v
+
+
 def merge_sparse(parts: List[Partials], slots) -> Partials:
     """Merge sparse partials by key (sum / min / max per slot op, max for HLL registers)."""
     parts = [p.compact() for p in parts]
@@ -286,6 +344,9 @@ def _agg_outputs_dev(prog, acc: torch.Tensor, skip) -> Dict[str, torch.Tensor]:
 
 SMALL_DENSE_WORDS = 1 << 20  # dense states up to this many accumulator words are fetched whole
 NATIVE_DECODE = True  # sparse finalize through post_scan.hip sparse_decode_kernel (tests compare both)
+# first-touch scans hand finalize their counted table (DeferredSparse): gather + decode in one
+# kernel (post_scan.hip touch_decode_kernel); False gathers in the scan as before (tests compare both)
+FUSED_TOUCH_DECODE = True
 _LUT_T = {torch.int32: 1, torch.int64: 2, torch.float64: 3}
 _OUT_NP = {0: np.int16, 1: np.int32, 2: np.int64, 3: np.float64, 4: np.float64, 5: np.int64}
 _OUT_W = {0: 2, 1: 4, 2: 8, 3: 8, 4: 8, 5: 8}
@@ -312,13 +373,19 @@ def _native_sparse(prog, parts: Partials, out_types, want_gid: bool):
     aggregator output is computed at its final width into one device buffer.  Returns
     (key_ids, derived_ids, derived_agg_vals, agg_host, gid, typed) or None when a column needs the
     general torch path (fixed-point float sums, float FD aggregate tables, > 16 columns)."""
-    g = parts.keys
-    if not g.is_cuda or _NO_DEVICE_DECODE:
-        return None
-    if not g.is_contiguous():  # (the kernel reads the ids as one contiguous int64 array)
-        g = g.contiguous()
-    dev = g.device
-    R = int(g.numel())
+    deferred = isinstance(parts, DeferredSparse) and parts.pending
+    if deferred:  # (still in the scan's table: on the device, R counted)
+        if _NO_DEVICE_DECODE:
+            return None
+        dev, R = parts.count.acc.device, parts.count.n
+    else:
+        g = parts.keys
+        if not g.is_cuda or _NO_DEVICE_DECODE:
+            return None
+        if not g.is_contiguous():  # (the kernel reads the ids as one contiguous int64 array)
+            g = g.contiguous()
+        dev = g.device
+        R = int(g.numel())
     specs, consts, typed = [], {}, {}
 
     def key_base(det):
@@ -405,14 +472,18 @@ def _native_sparse(prog, parts: Partials, out_types, want_gid: bool):
         offs.append(off)
         off = (off + R * _OUT_W[sp[1]] + 15) // 16 * 16
     nbytes = off
-    acc = parts.acc if parts.acc.is_contiguous() else parts.acc.contiguous()
-    out = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
     host = torch.empty(max(nbytes, 16), dtype=torch.uint8, pin_memory=True)
     from ..ops import native
 
-    native.load().sparse_decode(g.data_ptr(), acc.data_ptr(), R, int(acc.shape[1]) if acc.dim() == 2 else 1,
-                                [sp + (o,) for sp, o in zip(specs, offs)], out.data_ptr(), nbytes, host.data_ptr(),
-                                native._stream(dev))
+    cols = [sp + (o,) for sp, o in zip(specs, offs)]
+    if deferred:
+        native.touch_decode(parts.count, cols, nbytes, host)
+        parts.take()  # (emptied into ``host``: keys / acc stay None)
+    else:
+        acc = parts.acc if parts.acc.is_contiguous() else parts.acc.contiguous()
+        out = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        native.load().sparse_decode(g.data_ptr(), acc.data_ptr(), R, int(acc.shape[1]) if acc.dim() == 2 else 1, cols,
+                                    out.data_ptr(), nbytes, host.data_ptr(), native._stream(dev))
     hb = host.numpy()
     key_all = [None] * (nk + len(getattr(prog, "derived", ())))
     dag_vals = [None] * len(getattr(prog, "derived_aggs", ()))

@@ -51,6 +51,8 @@ __global__ void touch_count_kernel(const uint4* touch, int64_t nwords, uint64_t*
 __global__ void touch_gather_kernel(const uint64_t* words, int64_t nwords, const int64_t* offsets, int64_t* acc, int ns,
                                     const int64_t* init, unsigned char* touch, int64_t* out_idx, int64_t* out_acc);
 __global__ void sparse_decode_kernel(DecArgs a);
+__global__ void touch_decode_kernel(const uint64_t* words, int64_t nwords, const int64_t* offsets, int64_t* acc, int ns,
+                                    const int64_t* init, unsigned char* touch, DecArgs a);
 struct ResetArgs {
   int64_t* acc;
   const int64_t* init;
@@ -357,16 +359,13 @@ static void touch_gather(uint64_t words, int64_t nwords, uint64_t offsets, uint6
 // of ``nbytes`` into the pinned host buffer and one stream sync (GIL released while waiting).
 // cols: (kind, out, lut_t, slot, stride, card, add, orig, lut, div, off)
 using DecTuple = std::tuple<int, int, int, int, int64_t, int64_t, int64_t, uint64_t, uint64_t, double, int64_t>;
-static void sparse_decode(uint64_t idx, uint64_t acc, int64_t n, int ns, std::vector<DecTuple> cols, uint64_t out,
-                          int64_t nbytes, uint64_t host, uint64_t stream) {
+// (the column specs of both decode launchers: checked against the slot count, the row count and
+// the output size before anything is launched)
+static void dec_cols(sdo::DecArgs& a, const std::vector<DecTuple>& cols, int64_t n, int ns, int64_t nbytes) {
   if ((int)cols.size() > sdo::DEC_MAX_COLS) throw std::invalid_argument("sparse_decode: too many columns");
-  sdo::DecArgs a{};
-  a.idx = (const int64_t*)idx;
-  a.acc = (const int64_t*)acc;
   a.n = n;
   a.ns = ns;
   a.ncols = (int)cols.size();
-  a.out = (unsigned char*)out;
   for (size_t j = 0; j < cols.size(); ++j) {
     auto& c = a.c[j];
     c.kind = std::get<0>(cols[j]);
@@ -389,6 +388,15 @@ static void sparse_decode(uint64_t idx, uint64_t acc, int64_t n, int ns, std::ve
     const int64_t width = c.out == 0 ? 2 : (c.out == 1 ? 4 : 8);
     if (c.off < 0 || c.off % width || c.off + n * width > nbytes) throw std::invalid_argument("sparse_decode: column offset");
   }
+}
+
+static void sparse_decode(uint64_t idx, uint64_t acc, int64_t n, int ns, std::vector<DecTuple> cols, uint64_t out,
+                          int64_t nbytes, uint64_t host, uint64_t stream) {
+  sdo::DecArgs a{};
+  a.idx = (const int64_t*)idx;
+  a.acc = (const int64_t*)acc;
+  a.out = (unsigned char*)out;
+  dec_cols(a, cols, n, ns, nbytes);
   hipStream_t st = (hipStream_t)stream;
   if (n > 0 && !cols.empty()) {
     int64_t blocks = (n + 255) / 256;
@@ -399,6 +407,30 @@ static void sparse_decode(uint64_t idx, uint64_t acc, int64_t n, int ns, std::ve
   py::gil_scoped_release nogil;
   if (nbytes > 0) check(hipMemcpyAsync((void*)host, (const void*)out, nbytes, hipMemcpyDeviceToHost, st), "sparse_decode copy");
   wait_stream(st, "sparse_decode sync");
+}
+
+// First-touch gather + sparse decode in one kernel (post_scan.hip touch_decode_kernel): the ``n``
+// marked groups (the total touch_count gave) leave as final columns, their accumulator rows are
+// re-initialised and their bytes cleared.  The kernel stores straight into the pinned (device-
+// addressable) buffer ``host`` of ``nbytes``; the host may read it once this returns (GIL released
+// while waiting for the stream).
+static void touch_decode(uint64_t words, int64_t nwords, uint64_t offsets, uint64_t acc, int ns, uint64_t init,
+                         uint64_t touch, int64_t n, std::vector<DecTuple> cols, int64_t nbytes, uint64_t host,
+                         uint64_t stream) {
+  if (ns < 1 || ns > sdo::MAX_SLOTS) throw std::invalid_argument("touch_decode: slot count");
+  if (n < 0 || n > nwords * 64) throw std::invalid_argument("touch_decode: row count");
+  sdo::DecArgs a{};
+  a.out = (unsigned char*)host;
+  dec_cols(a, cols, n, ns, nbytes);
+  const int64_t nb = compact_blocks(nwords);
+  hipStream_t st = (hipStream_t)stream;
+  if (n > 0) {
+    hipLaunchKernelGGL(sdo::touch_decode_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const uint64_t*)words, nwords,
+                       (const int64_t*)offsets, (int64_t*)acc, ns, (const int64_t*)init, (unsigned char*)touch, a);
+    check(hipGetLastError(), "touch_decode_kernel launch");
+  }
+  py::gil_scoped_release nogil;
+  wait_stream(st, "touch_decode sync");
 }
 
 static void nonzero_mask(uint64_t base, int esize, int64_t n, int64_t stride, uint64_t words, uint64_t stream) {
@@ -1671,6 +1703,7 @@ PYBIND11_MODULE(_sdo_native, m) {
   m.def("touch_count", &touch_count);
   m.def("touch_gather", &touch_gather);
   m.def("sparse_decode", &sparse_decode);
+  m.def("touch_decode", &touch_decode);
   m.def("histogram", &histogram);
   m.def("reset_bufs", &reset_bufs);
   m.def("hll_pairs", &hll_pairs);

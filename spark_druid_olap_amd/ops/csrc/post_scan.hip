@@ -413,48 +413,111 @@ __global__ void __launch_bounds__(CW_THREADS) touch_gather_kernel(const uint64_t
 // float decode) -- written at their SQL width into ONE buffer (column c at byte offset off[c]) for
 // a single device-to-host copy, instead of a chain of torch element-wise / gather kernels and one
 // copy per column.
-__global__ void __launch_bounds__(256) sparse_decode_kernel(DecArgs a) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.n; r += stride) {
-    const int64_t g = a.idx[r];
-    for (int j = 0; j < a.ncols; ++j) {
-      const DecCol& c = a.c[j];
-      int64_t iv = 0;
-      double dv = 0.0;
-      bool is_d = false;
-      if (c.kind == 0) {
-        int64_t v = (g / c.stride) % c.card;
-        if (c.orig) v = c.orig[v];
-        if (c.lut_t == 1) iv = ((const int32_t*)c.lut)[v];
-        else if (c.lut_t == 2) iv = ((const int64_t*)c.lut)[v];
-        else if (c.lut_t == 3) { dv = ((const double*)c.lut)[v]; is_d = true; }
-        else iv = v;
-        iv += c.add;
-      } else if (c.kind == 4) {
-        iv = g;
+//
+// decode_row is one output row: every column's value from the group id ``g`` and the group's
+// accumulator row, stored at the column's SQL width at out + c.off + r * width
+// (sparse_decode_kernel and touch_decode_kernel share it).
+__device__ __forceinline__ void decode_row(const DecArgs& a, int64_t r, int64_t g, const int64_t* row) {
+  for (int j = 0; j < a.ncols; ++j) {
+    const DecCol& c = a.c[j];
+    int64_t iv = 0;
+    double dv = 0.0;
+    bool is_d = false;
+    if (c.kind == 0) {
+      int64_t v = (g / c.stride) % c.card;
+      if (c.orig) v = c.orig[v];
+      if (c.lut_t == 1) iv = ((const int32_t*)c.lut)[v];
+      else if (c.lut_t == 2) iv = ((const int64_t*)c.lut)[v];
+      else if (c.lut_t == 3) { dv = ((const double*)c.lut)[v]; is_d = true; }
+      else iv = v;
+      iv += c.add;
+    } else if (c.kind == 4) {
+      iv = g;
+    } else {
+      const int64_t v = row[c.slot];
+      if (c.kind == 1) {
+        iv = v;
+        if (c.div != 0.0) { dv = (double)v / c.div; is_d = true; }
+      } else if (c.kind == 2) {
+        iv = v >= 0 ? v : (v ^ 0x7FFFFFFFFFFFFFFFLL);
+        dv = __longlong_as_double(iv);
+        is_d = true;
       } else {
-        const int64_t v = a.acc[r * a.ns + c.slot];
-        if (c.kind == 1) {
-          iv = v;
-          if (c.div != 0.0) { dv = (double)v / c.div; is_d = true; }
-        } else if (c.kind == 2) {
-          iv = v >= 0 ? v : (v ^ 0x7FFFFFFFFFFFFFFFLL);
-          dv = __longlong_as_double(iv);
-          is_d = true;
-        } else {
-          iv = v;
-        }
-      }
-      unsigned char* o = a.out + c.off;
-      switch (c.out) {
-        case 0: ((int16_t*)o)[r] = (int16_t)iv; break;
-        case 1: ((int32_t*)o)[r] = (int32_t)iv; break;
-        case 2: ((int64_t*)o)[r] = iv; break;
-        case 3: ((double*)o)[r] = is_d ? dv : (double)iv; break;
-        case 4: ((int64_t*)o)[r] = is_d ? __double_as_longlong(dv) : iv; break;
-        default: ((int64_t*)o)[r] = (is_d ? (isfinite(dv) ? (int64_t)dv : 0) : iv); break;
+        iv = v;
       }
     }
+    unsigned char* o = a.out + c.off;
+    switch (c.out) {
+      case 0: ((int16_t*)o)[r] = (int16_t)iv; break;
+      case 1: ((int32_t*)o)[r] = (int32_t)iv; break;
+      case 2: ((int64_t*)o)[r] = iv; break;
+      case 3: ((double*)o)[r] = is_d ? dv : (double)iv; break;
+      case 4: ((int64_t*)o)[r] = is_d ? __double_as_longlong(dv) : iv; break;
+      default: ((int64_t*)o)[r] = (is_d ? (isfinite(dv) ? (int64_t)dv : 0) : iv); break;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) sparse_decode_kernel(DecArgs a) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.n; r += stride)
+    decode_row(a, r, a.idx[r], a.acc + r * a.ns);
+}
+
+// ---- First-touch gather and sparse decode in one pass (touch_gather_kernel + sparse_decode_kernel
+// without the (idx, acc row) arrays between them): a block takes the same 1024 mask words, so rows
+// leave in ascending group id.  The block first lists its marked groups in LDS (16-bit offsets
+// within the block's 65536 groups, TD_CHUNK at a time), then lane t of each pass decodes row t of
+// the list: every column's stores of a wave are 64 consecutive elements.  The accumulator row is
+// read where it lies, re-initialised and its touch byte cleared once its columns are stored.
+// ``a.n`` is the row count the output columns were sized for (a.idx / a.acc are not read).
+// ``a.out`` is the pinned host buffer itself: the stores cross the link as the rows are decoded
+// (no device copy of the result, no blit).  No fence in here: the host reads only after it has
+// waited for the stream, and the end of a kernel releases its stores at system scope; a fence of
+// every wave (L2 write-back + invalidate) made this kernel five times slower, one per block 25 us.
+constexpr int TD_CHUNK = 4096;
+
+__global__ void __launch_bounds__(CW_THREADS) touch_decode_kernel(const uint64_t* __restrict__ words, int64_t nwords,
+                                                                 const int64_t* __restrict__ offsets, int64_t* acc, int ns,
+                                                                 const int64_t* __restrict__ init,
+                                                                 unsigned char* __restrict__ touch, DecArgs a) {
+  __shared__ int lds[40];
+  __shared__ uint16_t ids[TD_CHUNK];
+  const int64_t w0 = ((int64_t)blockIdx.x * CW_THREADS + threadIdx.x) * CW_WORDS;
+  uint64_t w[CW_WORDS];
+  int c = 0;
+#pragma unroll
+  for (int i = 0; i < CW_WORDS; ++i) {
+    w[i] = (w0 + i < nwords) ? words[w0 + i] : 0ull;
+    c += __popcll(w[i]);
+  }
+  int total;
+  int p = block_excl_scan(c, lds, &total);
+  const int64_t base = offsets[blockIdx.x];
+  const int64_t gbase = (int64_t)blockIdx.x * (CW_THREADS * CW_WORDS * 64);
+  for (int lo = 0; lo < total; lo += TD_CHUNK) {
+    const int hi = min(lo + TD_CHUNK, total);
+    // this thread's marks at list positions [lo, hi): emitted bits are cleared, so the next chunk
+    // resumes where this one stopped
+#pragma unroll
+    for (int i = 0; i < CW_WORDS; ++i) {
+      while (w[i] && p < hi) {
+        const int b = __ffsll((unsigned long long)w[i]) - 1;
+        w[i] &= w[i] - 1;
+        ids[p - lo] = (uint16_t)(((threadIdx.x * CW_WORDS + i) << 6) + b);
+        ++p;
+      }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < hi - lo; t += CW_THREADS) {
+      const int64_t g = gbase + ids[t];
+      const int64_t r = base + lo + t;
+      int64_t* row = acc + g * ns;
+      if (r < a.n) decode_row(a, r, g, row);
+      for (int s = 0; s < ns; ++s) row[s] = init[s];
+      touch[g] = 0;
+    }
+    __syncthreads();
   }
 }
 

@@ -225,6 +225,17 @@ def touch_compact(touch: torch.Tensor, acc: torch.Tensor, init_row: torch.Tensor
     re-initialised to ``init_row`` and their bytes cleared (post_scan.hip touch_*: fused mask +
     count pass, offset scan, one gather / re-init / clear pass).  ``touch`` holds a multiple of 64
     bytes covering every row of ``acc`` [rows, nslots] int64."""
+    return touch_gather(touch_count(touch, acc, init_row))
+
+
+class TouchCount:
+    """A first-touch table after the count pass: the mask words, the per-block row offsets and the
+    number of marked groups ``n`` (read on the host: it sizes the outputs).  The accumulator rows
+    are still in the table and the bytes still set until ``touch_gather`` or ``touch_decode``."""
+    __slots__ = ("touch", "acc", "init_row", "words", "offs", "nw", "n")
+
+
+def touch_count(touch: torch.Tensor, acc: torch.Tensor, init_row: torch.Tensor) -> TouchCount:
     m = load()
     rows, ns = acc.shape
     nw = (rows + 63) // 64
@@ -232,19 +243,40 @@ def touch_compact(touch: torch.Tensor, acc: torch.Tensor, init_row: torch.Tensor
     assert acc.dtype == torch.int64 and acc.is_contiguous() and init_row.numel() == ns
     dev = acc.device
     nb = (nw + 1023) // 1024
-    words = torch.empty(max(nw, 1), dtype=torch.int64, device=dev)
-    counts = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
-    offs = torch.empty(max(nb, 1), dtype=torch.int64, device=dev)
-    total = torch.zeros(1, dtype=torch.int64, device=dev)
-    st = _stream(dev)
-    m.touch_count(touch.data_ptr(), nw, words.data_ptr(), counts.data_ptr(), offs.data_ptr(), total.data_ptr(), st)
-    n = int(total.item())
-    idx = torch.empty(n, dtype=torch.int64, device=dev)
-    out = torch.empty((n, ns), dtype=torch.int64, device=dev)
-    if n:
-        m.touch_gather(words.data_ptr(), nw, offs.data_ptr(), acc.data_ptr(), ns, init_row.data_ptr(),
-                       touch.data_ptr(), idx.data_ptr(), out.data_ptr(), st)
+    c = TouchCount()
+    c.touch, c.acc, c.init_row, c.nw, c.n = touch, acc, init_row, nw, 0
+    c.words = torch.empty(max(nw, 1), dtype=torch.int64, device=dev)
+    c.offs = torch.empty(max(nb, 1), dtype=torch.int64, device=dev)
+    if nb:
+        counts = torch.empty(nb, dtype=torch.int32, device=dev)
+        total = torch.empty(1, dtype=torch.int64, device=dev)  # (compact_offsets_kernel always writes it)
+        m.touch_count(touch.data_ptr(), nw, c.words.data_ptr(), counts.data_ptr(), c.offs.data_ptr(),
+                      total.data_ptr(), _stream(dev))
+        c.n = int(total.item())
+    return c
+
+
+def touch_gather(c: TouchCount):
+    """(group ids, accumulator rows) of a counted table; re-initialises the rows, clears the bytes."""
+    ns = int(c.acc.shape[1])
+    dev = c.acc.device
+    idx = torch.empty(c.n, dtype=torch.int64, device=dev)
+    out = torch.empty((c.n, ns), dtype=torch.int64, device=dev)
+    if c.n:
+        load().touch_gather(c.words.data_ptr(), c.nw, c.offs.data_ptr(), c.acc.data_ptr(), ns, c.init_row.data_ptr(),
+                            c.touch.data_ptr(), idx.data_ptr(), out.data_ptr(), _stream(dev))
     return idx, out
+
+
+def touch_decode(c: TouchCount, cols: list, nbytes: int, host: torch.Tensor) -> None:
+    """The counted table's groups as final result columns in the pinned buffer ``host`` (post_scan.hip
+    touch_decode_kernel: gather + sparse decode in one pass, ``cols`` as for ``sparse_decode``), rows
+    re-initialised and bytes cleared; returns once the columns are readable.  The kernel stores
+    into ``host`` itself (pinned memory is device-addressable): no device copy of the result."""
+    assert host.is_pinned() and host.dtype == torch.uint8 and host.numel() >= nbytes
+    load().touch_decode(c.words.data_ptr(), c.nw, c.offs.data_ptr(), c.acc.data_ptr(), int(c.acc.shape[1]),
+                        c.init_row.data_ptr(), c.touch.data_ptr(), c.n, cols, nbytes, host.data_ptr(),
+                        _stream(c.acc.device))
 
 
 def histogram(keys: torch.Tensor, nbins: int) -> torch.Tensor:
