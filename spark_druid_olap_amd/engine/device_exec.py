@@ -1511,7 +1511,7 @@ class PreparedEmit:
         ep.aops = [{"kind": D.A_ROWID, "col": -1, "expr": None, "filter": None, "slot": 0, "hll": -1}]
         ep.slots = [(D.S_SUM_I, 0)]
         ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
-        ep.comoments, ep.extremes, ep.histograms = [], [], []
+        ep.comoments, ep.extremes, ep.histograms, ep.central_moments = [], [], [], []
         ep.presence_only = False
         self.prog = ep
         self.dev = prog.ds.device
@@ -1583,7 +1583,7 @@ def theta_producer_prog(prog: ScanProgram, cols: List[str]) -> ScanProgram:
                for i, c in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(cols)
     ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
-    ep.comoments, ep.extremes, ep.histograms = [], [], []
+    ep.comoments, ep.extremes, ep.histograms, ep.central_moments = [], [], [], []
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("theta: program not eligible")
@@ -1773,7 +1773,7 @@ def quantile_producer_prog(prog: ScanProgram, cols: List[str], rowid: bool = Fal
                 for i, c in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(ep.aops)
     ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
-    ep.comoments, ep.extremes, ep.histograms = [], [], []
+    ep.comoments, ep.extremes, ep.histograms, ep.central_moments = [], [], [], []
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("quantile: program not eligible")
@@ -2060,6 +2060,74 @@ class PreparedComoments(_QvalRecords):
             PART_POOL.release(slab)
 
 
+CM_INT3, CM_INT4, CM_F64_SUM, CM_F64_DEV3, CM_F64_DEV4 = range(5)  # ops/csrc/central_moments.h CmMode
+CM_WORDS = (7, 11, 2, 3, 4)                                        # ... and cm_words (the tiers are MOM_TIERS)
+
+
+class PreparedCentralMoments(_QvalRecords):
+    """``skewness`` / ``kurtosis`` aggregators pushed into the scan: the quantile producer's records
+    (one pass for all columns), then per distinct column ONE accumulation of the power sums of
+    ops/csrc/central_moments.hip at the highest order an aggregator of the column asks for --
+    skewness(x) and kurtosis(x) share a state -- and per aggregator the finalise kernel.  Long /
+    decimal metrics whose stored values span less than 2^32 (whatever their width): ONE exact pass
+    over y = value - minimum, bitwise reproducible.  Double metrics and wider integer ranges: a sum
+    pass, the means, a pass over the deviations -- not exact.  Nothing is read back before the
+    result copy.  G <= ``max_g``."""
+
+    def __init__(self, prog: ScanProgram, central_moments: list, max_g: int):
+        from .lower import central_moments_exact
+
+        super().__init__(prog, sorted({c for _, c, _ in central_moments}), max_g, "central moments")
+        ds = prog.ds
+        # per distinct column: (value word offset, first pass's mode, order, pivot, is a double)
+        self.passes = {}
+        for c in self.cols:
+            order = max(o for _, cc, o in central_moments if cc == c)
+            if central_moments_exact(ds, c):
+                # (the ordered u64 of an integer is its two's complement with the sign bit flipped)
+                pivot = (_value_range(ds, c)[0] + (1 << 63)) & ((1 << 64) - 1)
+                self.passes[c] = (self.voff(c), CM_INT4 if order == 4 else CM_INT3, order, pivot, False)
+            else:
+                self.passes[c] = (self.voff(c), CM_F64_SUM, order, 0, ds.metrics[c].kind == "double")
+        self.sel = [(c, int(o)) for _, c, o in central_moments]
+        self.tiers = []  # (per distinct column of the last run: the tier its first pass took)
+
+    def values(self) -> list:
+        """Per aggregator its skewness / excess kurtosis [G] (host float64; NaN where the group's
+        rows hold fewer than two distinct values)."""
+        nat, st = native.load(), native._stream(self.dev)
+        dev, G = self.dev, self.G
+        pend = torch.empty(max(1, self.nch), dtype=torch.int32, device=dev)
+        slab = PART_POOL.acquire(dev, self.words)
+        try:
+            regions = self.produce(nat, st, slab, pend)
+            recs = slab.recs1.data_ptr()
+            states, self.tiers = {}, []
+            for c, (voff, mode, order, pivot, dbl) in self.passes.items():
+                a = torch.empty(G * CM_WORDS[mode], dtype=torch.int64, device=dev)
+                tier = nat.central_moments_accum(recs, self.rw, voff, *regions, mode, -1, pivot, dbl, 0, a.data_ptr(), st)
+                b, fmode = None, mode
+                if mode == CM_F64_SUM:
+                    fmode = CM_F64_DEV4 if order == 4 else CM_F64_DEV3
+                    mean = torch.empty(G, dtype=torch.float64, device=dev)
+                    b = torch.empty(G * CM_WORDS[fmode], dtype=torch.int64, device=dev)
+                    nat.central_moments_mean(a.data_ptr(), G, mean.data_ptr(), st)
+                    nat.central_moments_accum(recs, self.rw, voff, *regions, fmode, -1, 0, dbl, mean.data_ptr(),
+                                              b.data_ptr(), st)
+                states[c] = (a, b, fmode)
+                self.tiers.append(MOM_TIERS[tier])
+            res = []
+            for c, order in self.sel:
+                a, b, fmode = states[c]
+                out = torch.empty(G, dtype=torch.float64, device=dev)
+                nat.central_moments_final(a.data_ptr(), b.data_ptr() if b is not None else 0, G, fmode, order,
+                                          out.data_ptr(), st)
+                res.append(out)
+            return [r.cpu().numpy() for r in res]
+        finally:
+            PART_POOL.release(slab)
+
+
 EXT_PACKED, EXT_WIDE_VAL, EXT_WIDE_ROW = range(3)  # ops/csrc/extreme.h ExtMode
 EXT_MAX, EXT_MIN, EXT_BOTH = 1, 2, 3              # ... ExtDirs (the tiers are MOM_TIERS)
 EXT_TYPES = {torch.int8: 0, torch.uint8: 1, torch.int16: 2, torch.int32: 3, torch.int64: 4, torch.float32: 5,
@@ -2220,7 +2288,7 @@ def distinct_producer_prog(prog: ScanProgram, cols: list) -> ScanProgram:
                 "filt_off": off, "filt_len": n} for i, (c, (off, n)) in enumerate(cols)]
     ep.slots = [(D.S_SUM_I, 0)] * len(cols)
     ep.nhll, ep.stored_hll, ep.thetas, ep.quantiles, ep.distincts, ep.moments, ep.packed = 0, [], [], [], [], [], {}
-    ep.comoments, ep.extremes, ep.histograms = [], [], []
+    ep.comoments, ep.extremes, ep.histograms, ep.central_moments = [], [], [], []
     ep.presence_only = False
     if not J.part_eligible(ep) or J.part_hashed(ep):
         raise RuntimeError("distinct: program not eligible")
@@ -2443,13 +2511,14 @@ PACK_RECORDS = True
 
 
 def _value_range(ds, name: str):
-    """(min, max) of a column's stored values (cached per datasource)."""
+    """(min, max) of a column's stored values, without the zero padding behind the last row (cached
+    per datasource)."""
     cache = ds.__dict__.setdefault("_value_ranges", {})
     r = cache.get(name)
     if r is None:
         from .lower import column_tensor
 
-        t = column_tensor(ds, name)
+        t = column_tensor(ds, name)[:ds.num_rows]
         if t.numel() == 0 or t.is_floating_point():
             r = cache[name] = False
         else:

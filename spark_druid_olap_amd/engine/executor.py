@@ -506,7 +506,10 @@ class PreparedQuery:
                 co_tiers = self._comoments(self._full_prog, cols)
                 ext_tiers = self._extremes(self._full_prog, cols)
                 hist_tiers = self._histograms(self._full_prog, cols)
+                cm_tiers = self._central_moments(self._full_prog, cols)
                 res = self._post(prog, cols)
+                if cm_tiers:
+                    res.stats["central_moments_device"] = cm_tiers
                 if hist_tiers:
                     res.stats["histogram_device"] = hist_tiers
                 if tiers:
@@ -1473,6 +1476,60 @@ class PreparedQuery:
         if ep is False:
             return None
         return ep.counts()
+
+    # ------------------------------------------------------------------ skewness / kurtosis
+    def _central_moments(self, prog: ScanProgram, cols: Dict[str, np.ndarray]) -> Optional[list]:
+        """``skewness`` / ``kurtosis`` aggregators: per group the statistic of the selected rows'
+        values, a float64 column (NaN where the rows hold one value only) that HAVING, ordering and
+        post-aggregations read like a double sum.  On the native GPU engine the power sums answer
+        (engine/device_exec.py PreparedCentralMoments: exact for long / decimal metrics of a range
+        below 2^32); everywhere else -- CPU, the reference executor, hashed keys, more than
+        QUANTILE_SELECT_MAX_G groups -- a centred two-pass in float64 does (ops/reference.py
+        group_central_moments), which is NOT exact.  Returns the tier per distinct column when the
+        device sums answered (the result's ``central_moments_device`` stats entry), else None."""
+        if not prog.central_moments:
+            return None
+        gid_order = np.asarray(cols["__gid__"], dtype=np.int64)
+        fused = self._central_moments_fused(prog)
+        if fused is not None:
+            for (name, _, _), res in zip(prog.central_moments, fused):
+                ok = (gid_order >= 0) & (gid_order < len(res))
+                cols[name] = np.where(ok, res[np.clip(gid_order, 0, max(0, len(res) - 1))], np.nan)
+            return list(self._central_moments_prep.tiers)
+        from ..ops.reference import _rows, compute_keys, eval_bexpr, group_central_moments
+        from .lower import column_tensor
+
+        ds = self.ds
+        rows = _rows(prog) if not prog.empty else torch.zeros(0, dtype=torch.int64, device=ds.device)
+        if rows.numel():
+            rows = rows[eval_bexpr(prog, prog.bexpr, rows)]
+        keys = compute_keys(prog, rows)
+        for name, col, order in prog.central_moments:
+            # (both statistics are invariant under a decimal's scale)
+            gids, val = group_central_moments(keys, column_tensor(ds, col)[rows].to(torch.float64), order)
+            gids, val = gids.cpu().numpy(), val.cpu().numpy()
+            at = np.clip(np.searchsorted(gids, gid_order), 0, max(0, len(gids) - 1))
+            cols[name] = np.where(gids[at] == gid_order, val[at], np.nan) if len(gids) else \
+                np.full(len(gid_order), np.nan)
+        return None
+
+    def _central_moments_fused(self, prog: ScanProgram) -> Optional[list]:
+        """Per skewness / kurtosis aggregator its values [G] from the device power sums, or None
+        where they do not apply (CPU, hashed or ineligible keys, too many groups, an empty shard)."""
+        if prog.empty or self.ds.device.type != "cuda" or not self.engine.use_native:
+            return None
+        cp = self.__dict__.get("_central_moments_prep")
+        if cp is None:
+            try:
+                from .device_exec import PreparedCentralMoments
+
+                cp = PreparedCentralMoments(prog, prog.central_moments, QUANTILE_SELECT_MAX_G)
+            except RuntimeError:
+                cp = False
+            self._central_moments_prep = cp
+        if cp is False:
+            return None
+        return cp.values()
 
     # ------------------------------------------------------------------ post processing
     def _post(self, prog: ScanProgram, cols: Dict[str, np.ndarray]) -> QueryResult:

@@ -378,6 +378,8 @@ class ScanProgram:
     extremes: List[Tuple[str, str, str, bool]] = field(default_factory=list)
     # fixed-bucket histograms: (name, metric, edges as Fractions, outlier mode)
     histograms: List[Tuple[str, str, tuple, str]] = field(default_factory=list)
+    # skewness / kurtosis: (name, metric, order: 3 skewness, 4 kurtosis)
+    central_moments: List[Tuple[str, str, int]] = field(default_factory=list)
     luts: Dict[str, torch.Tensor] = field(default_factory=dict)       # dim -> f64 value per dictionary id
     lut_ptrs: Dict[float, torch.Tensor] = field(default_factory=dict)  # E_LUT operand -> its table
     # grouping keys functionally determined by a packed key: (key, index of determinant in keys,
@@ -396,12 +398,12 @@ class ScanProgram:
     @property
     def needs_rows(self) -> bool:
         """Some aggregator reads the selected rows themselves (theta KMV, order statistics, exact
-        distinct counts, variances, covariances, values at an extreme, bucket counts), not an
-        accumulator: strategies that keep only accumulators decline, the executor answers it after the
-        scan (engine/executor.py _theta / _quantile / _distinct / _moments / _comoments / _extremes /
-        _histograms)."""
+        distinct counts, variances, covariances, values at an extreme, bucket counts, skewness /
+        kurtosis), not an accumulator: strategies that keep only accumulators decline, the executor
+        answers it after the scan (engine/executor.py _theta / _quantile / _distinct / _moments /
+        _comoments / _extremes / _histograms / _central_moments)."""
         return bool(self.thetas or self.quantiles or self.distincts or self.moments or self.comoments or
-                    self.extremes or self.histograms)
+                    self.extremes or self.histograms or self.central_moments)
 
     @property
     def nhll_total(self) -> int:
@@ -457,6 +459,17 @@ def column_tensor(ds: DataSource, name: str) -> torch.Tensor:
         if t is not None:
             return t
     raise LoweringError(f"unknown column {name!r} in datasource {ds.name}")
+
+
+def central_moments_exact(ds: DataSource, name: str) -> bool:
+    """Whether skewness / kurtosis of the metric take the exact integer sums (a long / decimal metric
+    whose stored values span less than 2^32: ops/csrc/central_moments.h) and not the f64 passes."""
+    from .device_exec import _value_range
+
+    if ds.metrics[name].kind == "double":
+        return False
+    rng = _value_range(ds, name)
+    return rng is not None and rng[1] - rng[0] < (1 << 32)
 
 
 class Lowerer:
@@ -1413,6 +1426,26 @@ class Lowerer:
                                         "(deterministic mode)")
             kind = "corr" if what == "correlation" else "cov-samp" if a.estimator == "sample" else "cov-pop"
             prog.comoments.append((a.name, a.fieldName, a.fieldName2, kind))
+            prog.aggs.append(AggOut(a.name, "moment", out_type="double", combine="moment"))
+            return
+        if isinstance(a, (S.SkewnessAggregationSpec, S.KurtosisAggregationSpec)):
+            what = a.type
+            if self.world is not None and self.world.distributed:
+                # (as variance: the integer states are additive but not reduced across ranks yet)
+                raise LoweringError(f"{what} aggregators are not answered across ranks")
+            m = ds.metrics.get(a.fieldName)
+            if m is None:
+                raise LoweringError(f"{what} over {a.fieldName!r}: not a metric")
+            if m.sketch is not None or m.kind not in ("long", "double", "decimal"):
+                raise LoweringError(f"{what} over the sketch metric {a.fieldName!r}")
+            if filt is not None:
+                raise LoweringError(f"{what} inside a filtered aggregator is not supported")
+            if self.deterministic and not central_moments_exact(ds, a.fieldName):
+                # (double metrics and integers of range >= 2^32 take two passes of f64 atomic adds;
+                # a narrower integer range adds integers only and stays bitwise reproducible)
+                raise LoweringError(f"{what} over {a.fieldName!r} goes through doubles: not bitwise reproducible "
+                                    "(deterministic mode)")
+            prog.central_moments.append((a.name, a.fieldName, 3 if what == "skewness" else 4))
             prog.aggs.append(AggOut(a.name, "moment", out_type="double", combine="moment"))
             return
         if isinstance(a, (S.MaxByAggregationSpec, S.MinByAggregationSpec)):

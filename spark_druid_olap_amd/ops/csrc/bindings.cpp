@@ -26,6 +26,7 @@
 #include "distinct.h"
 #include "moments.h"
 #include "comoments.h"
+#include "central_moments.h"
 #include "extreme.h"
 #include "histogram.h"
 
@@ -161,6 +162,24 @@ __global__ void co_global_regions_kernel(const uint32_t* __restrict__ recs, int 
 __global__ void co_mean_kernel(const uint64_t* sum, int G, double* mean);
 __global__ void co_final_kernel(const uint64_t* a, const uint64_t* b, int G, int mode, int sq, int kind, int ddof,
                                 double div, double* out);
+// central_moments.hip (shapes: central_moments.h)
+template <int MODE>
+__global__ void cm_few_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff,
+                                      const uint32_t* __restrict__ seg_lo, const uint32_t* __restrict__ seg_hi,
+                                      int64_t nseg, uint32_t G, uint64_t pivot, int dbl,
+                                      const double* __restrict__ mean, uint64_t* __restrict__ state);
+template <int MODE>
+__global__ void cm_lds_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff,
+                                      const uint32_t* __restrict__ seg_lo, const uint32_t* __restrict__ seg_hi,
+                                      int64_t nseg, uint32_t g0, uint32_t GL, uint64_t pivot, int dbl,
+                                      const double* __restrict__ mean, uint64_t* __restrict__ state);
+template <int MODE>
+__global__ void cm_global_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff,
+                                         const uint32_t* __restrict__ seg_lo, const uint32_t* __restrict__ seg_hi,
+                                         int64_t nseg, uint32_t G, uint64_t pivot, int dbl,
+                                         const double* __restrict__ mean, uint64_t* __restrict__ state);
+__global__ void cm_mean_kernel(const uint64_t* sum, int G, double* mean);
+__global__ void cm_final_kernel(const uint64_t* a, const uint64_t* b, int G, int mode, int order, double* out);
 // extreme.hip (shapes: extreme.h)
 template <int MODE, int DIRS>
 __global__ void ext_few_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff,
@@ -1292,6 +1311,98 @@ static void comoments_final(uint64_t a, uint64_t b, int64_t G, int mode, bool sq
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-group power sums up to order 4 over the same records (central_moments.hip): one accumulation
+// pass of `mode` (central_moments.h CmMode) over the value at `voff` into the cleared [G][W] u64
+// `state`.  Integer modes: `pivot` is the ordered u64 of the column's minimum, and the caller
+// vouches that max - min < 2^32.  f64 modes: `dbl` says the column is a double (else its integer is
+// converted); the DEV modes read the group means (`mean`, [G] f64: central_moments_mean).  `tier` -1
+// picks the tier from G (central_moments.h cm_tier); 0..2 asks for one that holds G.  Returns the
+// tier used.
+template <int MODE>
+static void cm_launch(int tier, unsigned grid, hipStream_t s, const uint32_t* recs, int rw, int voff,
+                      const uint32_t* seg_lo, const uint32_t* seg_hi, int64_t nseg, uint32_t G, uint64_t pivot, int dbl,
+                      const double* mean, uint64_t* state) {
+  if (tier == sdo::CM_TIER_FEW) {
+    hipLaunchKernelGGL(sdo::cm_few_regions_kernel<MODE>, dim3(grid), dim3(256), 0, s, recs, rw, voff, seg_lo, seg_hi,
+                       nseg, G, pivot, dbl, mean, state);
+  } else if (tier == sdo::CM_TIER_LDS) {
+    // one pass per key slice of (nearly) equal size, each table within the LDS budget
+    const uint32_t cap = (uint32_t)sdo::cm_lds_groups(MODE);
+    const uint32_t slices = (G + cap - 1) / cap, GL = (G + slices - 1) / slices;
+    for (uint32_t g0 = 0; g0 < G; g0 += GL) {
+      const uint32_t n = std::min(GL, G - g0);
+      hipLaunchKernelGGL(sdo::cm_lds_regions_kernel<MODE>, dim3(grid), dim3(256),
+                         n * (size_t)sdo::cm_state_bytes(MODE), s, recs, rw, voff, seg_lo, seg_hi, nseg, g0, n, pivot,
+                         dbl, mean, state);
+    }
+  } else {
+    hipLaunchKernelGGL(sdo::cm_global_regions_kernel<MODE>, dim3(grid), dim3(256), 0, s, recs, rw, voff, seg_lo,
+                       seg_hi, nseg, G, pivot, dbl, mean, state);
+  }
+}
+
+static int central_moments_accum(uint64_t recs, int rw, int voff, uint64_t seg_lo, uint64_t seg_hi, int64_t nseg,
+                                 int64_t G, int mode, int tier, uint64_t pivot, bool dbl, uint64_t mean, uint64_t state,
+                                 uint64_t stream) {
+  qsel_check(rw, voff, G);
+  if (mode < sdo::CM_INT3 || mode > sdo::CM_F64_DEV4) throw std::invalid_argument("central_moments_accum: mode");
+  if (nseg < 0 || !state || (mode > sdo::CM_F64_SUM && !mean))
+    throw std::invalid_argument("central_moments_accum: arguments");
+  const int fit = sdo::cm_tier(mode, G);
+  if (tier < 0) tier = fit;
+  if (tier > sdo::CM_TIER_GLOBAL || tier < fit)
+    throw std::invalid_argument("central_moments_accum: tier does not hold G");
+  const int W = sdo::cm_words(mode);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(sdo::qsel_clear_kernel, dim3(grid_for(G * W * 2, 256, 4096)), dim3(256), 0, s, (uint32_t*)state,
+                     G * W * 2);
+  check(hipGetLastError(), "central moments clear launch");
+  if (nseg == 0) return tier;
+  // (the grids of moments_accum: few / lds workgroups end with a flush onto the same global words)
+  const unsigned grid = (unsigned)std::min<int64_t>(nseg, tier == sdo::CM_TIER_GLOBAL ? 4096 : 1024);
+  const uint32_t* r = (const uint32_t*)recs;
+  const uint32_t *lo = (const uint32_t*)seg_lo, *hi = (const uint32_t*)seg_hi;
+  const double* mu = (const double*)mean;
+  uint64_t* st = (uint64_t*)state;
+#define SDO_CM_CASE(M) \
+  cm_launch<sdo::M>(tier, grid, s, r, rw, voff, lo, hi, nseg, (uint32_t)G, pivot, dbl ? 1 : 0, mu, st)
+  switch (mode) {
+    case sdo::CM_INT3: SDO_CM_CASE(CM_INT3); break;
+    case sdo::CM_INT4: SDO_CM_CASE(CM_INT4); break;
+    case sdo::CM_F64_SUM: SDO_CM_CASE(CM_F64_SUM); break;
+    case sdo::CM_F64_DEV3: SDO_CM_CASE(CM_F64_DEV3); break;
+    default: SDO_CM_CASE(CM_F64_DEV4); break;
+  }
+#undef SDO_CM_CASE
+  check(hipGetLastError(), "central moments accumulation launch");
+  return tier;
+}
+
+// mean[g] = sum x / n from a CM_F64_SUM state (0 for an empty group)
+static void central_moments_mean(uint64_t sum, int64_t G, uint64_t mean, uint64_t stream) {
+  if (G <= 0 || G > (1 << 20) || !sum || !mean) throw std::invalid_argument("central_moments_mean: arguments");
+  hipLaunchKernelGGL(sdo::cm_mean_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const uint64_t*)sum, (int)G, (double*)mean);
+  check(hipGetLastError(), "cm_mean_kernel launch");
+}
+
+// out[g] (f64) = the skewness (`order` 3) or excess kurtosis (4), NaN where the group's second
+// moment is 0.  Integer modes: `a` the accumulated state (order 4 needs CM_INT4); CM_F64_DEV3 / 4:
+// `a` the CM_F64_SUM state (the counts), `b` the DEV state (order 4 needs CM_F64_DEV4).
+static void central_moments_final(uint64_t a, uint64_t b, int64_t G, int mode, int order, uint64_t out,
+                                  uint64_t stream) {
+  if (G <= 0 || G > (1 << 20) || !a || !out) throw std::invalid_argument("central_moments_final: arguments");
+  if (mode == sdo::CM_F64_SUM || mode < sdo::CM_INT3 || mode > sdo::CM_F64_DEV4)
+    throw std::invalid_argument("central_moments_final: mode");
+  if ((mode > sdo::CM_F64_SUM && !b) || (order != 3 && order != 4) ||
+      (order == 4 && mode != sdo::CM_INT4 && mode != sdo::CM_F64_DEV4))
+    throw std::invalid_argument("central_moments_final: arguments");
+  hipLaunchKernelGGL(sdo::cm_final_kernel, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const uint64_t*)a, (const uint64_t*)b, (int)G, mode, order, (double*)out);
+  check(hipGetLastError(), "cm_final_kernel launch");
+}
+
+// ---------------------------------------------------------------------------------------------
 // max_by / min_by: per-group packed-key extremes over (key, row id, ordered values ...) records
 // (extreme.hip).  One accumulation pass of `mode` (extreme.h ExtMode) for the directions `dirs`
 // (ExtDirs) over the value at `voff` (0: none, the ordering is the row id alone -- EXT_PACKED only)
@@ -1746,6 +1857,9 @@ PYBIND11_MODULE(_sdo_native, m) {
   m.def("comoments_accum", &comoments_accum);
   m.def("comoments_mean", &comoments_mean);
   m.def("comoments_final", &comoments_final);
+  m.def("central_moments_accum", &central_moments_accum);
+  m.def("central_moments_mean", &central_moments_mean);
+  m.def("central_moments_final", &central_moments_final);
   m.def("extreme_accum", &extreme_accum);
   m.def("extreme_final", &extreme_final);
   m.def("histogram_accum", &histogram_accum);

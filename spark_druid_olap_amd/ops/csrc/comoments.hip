@@ -117,49 +117,7 @@ __device__ __forceinline__ void co_load(const uint32_t* __restrict__ recs, int r
 // ---------------------------------------------------------------------------------------------
 // few groups: one reduce-scatter of the state across the wave per distinct key
 
-// the 32-bit value of lane ^ 2^S: quad permutes (DPP) inside a quad, ds_swizzle's xor mask inside
-// 32 lanes, a bpermute across the halves.  All 64 lanes must be live.
-template <int S>
-__device__ __forceinline__ uint32_t co_xchg32(uint32_t v) {
-  if constexpr (S == 0) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false);  // [1,0,3,2]
-  else if constexpr (S == 1) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false);  // [2,3,0,1]
-  else if constexpr (S < 5) return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, ((1 << S) << 10) | 0x1f);
-  else return (uint32_t)__shfl_xor((int)v, 32, 64);
-}
-
-template <int S>
-__device__ __forceinline__ uint64_t co_xchg(uint64_t v) {
-  return (uint64_t)co_xchg32<S>((uint32_t)v) | ((uint64_t)co_xchg32<S>((uint32_t)(v >> 32)) << 32);
-}
-
-// Sums the P words a[] of every lane over the wave.  Step S (H = P / 2^(S+1) words kept): a lane
-// whose bit S is clear keeps a[0..H) and hands a[H..2H) to lane ^ 2^S, which does the opposite; once
-// one word a lane is left the remaining steps add it across.  Lane l < P ends with the wave's total
-// of word co_word_of<P>(l) in a[0].
-template <bool F, int H, int S, int P>
-__device__ __forceinline__ void co_reduce_scatter(uint64_t (&a)[P], int lane) {
-  if constexpr (H >= 1) {
-    const bool up = (lane >> S) & 1;
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-      const uint64_t send = up ? a[j] : a[j + H];
-      const uint64_t keep = up ? a[j + H] : a[j];
-      a[j] = mom_add(F, keep, co_xchg<S>(send));
-    }
-    co_reduce_scatter<F, H / 2, S + 1, P>(a, lane);
-  } else if constexpr (S < 6) {
-    a[0] = mom_add(F, a[0], co_xchg<S>(a[0]));
-    co_reduce_scatter<F, 0, S + 1, P>(a, lane);
-  }
-}
-
-template <int P>
-__device__ __forceinline__ int co_word_of(int lane) {  // (the low log2 P bits of the lane, reversed)
-  int idx = 0;
-#pragma unroll
-  for (int s = 0; (P >> (s + 1)) >= 1; ++s) idx += ((lane >> s) & 1) * (P >> (s + 1));
-  return idx;
-}
+// (co_reduce_scatter, co_word_of: moments_dev.h)
 
 template <int MODE, bool SQ>
 __global__ void __launch_bounds__(256) co_few_regions_kernel(const uint32_t* __restrict__ recs, int rw, int voff_x,

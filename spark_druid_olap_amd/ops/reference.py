@@ -457,6 +457,29 @@ def group_comoments(keys: torch.Tensor, x: torch.Tensor, y: torch.Tensor, kind: 
     return gids, torch.where(ok, torch.clamp(r, -1.0, 1.0), nan)
 
 
+def group_central_moments(keys: torch.Tensor, v: torch.Tensor, order: int):
+    """Skewness (``order`` 3: sqrt(n) M3 / M2^1.5) or excess kurtosis (4: n M4 / M2^2 - 3) by group
+    in float64, centred two-pass: (group keys ascending, value per group) of the (group key, value)
+    pairs; NaN where the group's second central moment is 0.  NOT exact, as ``group_variances`` --
+    the engine's answer wherever ops/csrc/central_moments.hip does not apply."""
+    gids, inv, cnt = torch.unique(keys.to(torch.int64), return_inverse=True, return_counts=True)
+    v = v.to(torch.float64)
+    n = cnt.to(torch.float64)
+
+    def by_group(x):
+        return torch.zeros(len(gids), dtype=torch.float64, device=v.device).index_add_(0, inv, x)
+
+    d = v - (by_group(v) / n)[inv]
+    d = d - (by_group(d) / n)[inv]  # (the rounded mean's residue)
+    d2 = d * d
+    m2 = by_group(d2)
+    ok = m2 > 0
+    m2 = torch.where(ok, m2, torch.ones_like(n))
+    val = torch.sqrt(n) * by_group(d2 * d) / (m2 * torch.sqrt(m2)) if order == 3 else \
+        n * by_group(d2 * d2) / (m2 * m2) - 3.0
+    return gids, torch.where(ok, val, torch.full_like(n, float("nan")))
+
+
 def group_extremes(keys: torch.Tensor, y: torch.Tensor, rows: torch.Tensor, is_max: bool):
     """max_by / min_by by group: (group keys ascending, the row id at the lexicographic maximum /
     minimum of (y, row id)) of the (group key, ordering value y, row id) triples -- among rows that

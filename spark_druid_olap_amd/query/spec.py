@@ -538,6 +538,28 @@ class VarianceAggregationSpec(Spec, _Decodable):
     type: str = "variance"
 
 
+@_register("aggregation", "skewness")
+@dataclass
+class SkewnessAggregationSpec(Spec, _Decodable):
+    """Skewness of a long / decimal / double metric over the selected rows, Spark's
+    ``sqrt(n) M3 / M2^1.5`` with ``Mk`` the sum of (x - mean)^k: a double, NaN for a group whose
+    rows hold one value only.  The type name is this project's own, as ``covariance``."""
+    name: str
+    fieldName: str
+    type: str = "skewness"
+
+
+@_register("aggregation", "kurtosis")
+@dataclass
+class KurtosisAggregationSpec(Spec, _Decodable):
+    """Excess kurtosis of a long / decimal / double metric over the selected rows, Spark's
+    ``n M4 / M2^2 - 3``: a double, NaN for a group whose rows hold one value only.  The type name is
+    this project's own, as ``covariance``."""
+    name: str
+    fieldName: str
+    type: str = "kurtosis"
+
+
 @_register("aggregation", "covariance")
 @dataclass
 class CovarianceAggregationSpec(Spec, _Decodable):

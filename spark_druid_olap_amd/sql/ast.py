@@ -144,7 +144,7 @@ AGG_FUNCS = {"count", "sum", "min", "max", "avg", "mean", "approx_count_distinct
              "stddev", "stddev_samp", "stddev_pop", "variance", "var_samp", "var_pop", "collect_set",
              "collect_list", "grouping", "grouping_id", "percentile", "median", "percentile_approx",
              "approx_percentile", "corr", "covar_samp", "covar_pop", "max_by", "min_by",
-             "histogram"}
+             "histogram", "skewness", "kurtosis"}
 # exact order statistics (query/spec.py QuantilesAggregationSpec)
 QUANTILE_FUNCS = {"percentile", "median", "percentile_approx", "approx_percentile"}
 # two-column statistics (query/spec.py CovarianceAggregationSpec / CorrelationAggregationSpec)
@@ -153,6 +153,8 @@ COMOMENT_FUNCS = {"corr", "covar_samp", "covar_pop"}
 EXTREME_FUNCS = {"max_by", "min_by"}
 # fixed-bucket counts (query/spec.py FixedBucketsHistogramAggregationSpec)
 HISTOGRAM_FUNCS = {"histogram"}
+# third / fourth standardised moments (query/spec.py SkewnessAggregationSpec / KurtosisAggregationSpec)
+CENTRAL_MOMENT_FUNCS = {"skewness", "kurtosis"}
 
 
 @dataclass(frozen=True, repr=False)

@@ -702,7 +702,8 @@ class DruidRewriter:
                 if isinstance(spec_, (S.QuantilesAggregationSpec, S.VarianceAggregationSpec,
                                       S.CovarianceAggregationSpec, S.CorrelationAggregationSpec,
                                       S.MaxByAggregationSpec, S.MinByAggregationSpec,
-                                      S.FixedBucketsHistogramAggregationSpec)):
+                                      S.FixedBucketsHistogramAggregationSpec,
+                                      S.SkewnessAggregationSpec, S.KurtosisAggregationSpec)):
                     shared[id(spec_)] = r
                 drefs.append(r)
                 columns.append((spec_.name, t, part[2] if len(part) > 2 else "value"))
@@ -964,7 +965,41 @@ class DruidRewriter:
             return self._extreme_agg(pf, call, names, rolled)
         if n in A.HISTOGRAM_FUNCS:
             return self._histogram_agg(pf, call, names, rolled)
+        if n in A.CENTRAL_MOMENT_FUNCS:
+            return self._central_moment_agg(pf, call, names, rolled)
         raise NotPushable(f"aggregate {n} is not pushable")
+
+    def _central_moment_agg(self, pf: PF, call: A.Call, names: "_Names", rolled: bool):
+        """skewness / kurtosis over a plain long / decimal / double metric -> ONE ``skewness`` /
+        ``kurtosis`` aggregator per (function, column) of the query.  An undefined value is NaN, which
+        the result conversion turns into NULL as the host plan's.  The power sums are per shard: a
+        distributed session answers on the host."""
+        from ..engine.lower import central_moments_exact
+
+        n = call.name
+        if call.distinct:
+            raise NotPushable(f"{n}(DISTINCT)")
+        if rolled or getattr(pf.table.info.datasource, "rollup", False):
+            raise NotPushable(f"{n} over a rolled-up datasource")
+        if self.session.engine.world.distributed:
+            raise NotPushable(f"{n} across ranks")
+        x = call.args[0] if len(call.args) == 1 else None
+        if not isinstance(x, A.Ref):
+            raise NotPushable(f"{n} over an expression")
+        c = self._column(pf, x)
+        ds = pf.table.info.datasource
+        m = ds.metrics.get(c.druid_column) if c.is_metric else None
+        if m is None or m.sketch is not None or m.kind not in ("long", "decimal", "double"):
+            raise NotPushable(f"{n} over {c.column}: not a long / decimal / double metric")
+        if (self.session.engine.deterministic or bool(self.conf.typed("spark.sparklinedata.druid.deterministic"))) \
+                and not central_moments_exact(ds, c.druid_column):
+            raise NotPushable(f"{n} over {c.column} goes through doubles: deterministic mode")
+        key = (n, c.druid_column)
+        spec = names.central_moments.get(key)
+        if spec is None:
+            cls = S.SkewnessAggregationSpec if n == "skewness" else S.KurtosisAggregationSpec
+            spec = names.central_moments[key] = cls(names.agg(), c.druid_column)
+        return [(spec, "double")], lambda rs: rs[0]
 
     def _comoment_agg(self, pf: PF, call: A.Call, names: "_Names", rolled: bool):
         """corr / covar_samp / covar_pop over two plain long / decimal / double metrics -> ONE
@@ -1618,6 +1653,7 @@ class _Names:
         self.comoments: Dict[tuple, object] = {}  # (column x, column y, function) -> its one aggregator
         self.extremes: Dict[tuple, object] = {}   # (payload, ordering column, function) -> its one aggregator
         self.histograms: Dict[tuple, object] = {}  # (column, form, limits) -> its one aggregator
+        self.central_moments: Dict[tuple, object] = {}  # (function, column) -> its one aggregator
 
     def agg(self) -> str:
         self.n += 1

@@ -1025,6 +1025,8 @@ def _agg_one(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, n: int, out_t:
         return _agg_quantile(call, fr, codes, ng, out_t)
     if name in A.COMOMENT_FUNCS:
         return _agg_comoment(call, fr, codes, ng, out_t)
+    if name in A.CENTRAL_MOMENT_FUNCS:
+        return _agg_central_moment(call, fr, codes, ng, out_t)
     if name in A.EXTREME_FUNCS:
         return _agg_extreme(call, fr, codes, ng, out_t)
     if name in A.HISTOGRAM_FUNCS:
@@ -1133,6 +1135,30 @@ def _agg_extreme(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, out_t: str
     at = df.groupby("g")["i"].last() if call.name == "max_by" else df.groupby("g")["i"].first()
     r = pd.Series(x.to_numpy(dtype=object)[at.to_numpy()], index=at.index).reindex(range(ng))
     return to_series(r, out_t)
+
+
+def _agg_central_moment(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, out_t: str) -> pd.Series:
+    """skewness (sqrt(n) M3 / M2^1.5) / kurtosis (n M4 / M2^2 - 3) per group (``ng`` = 1 without
+    GROUP BY) over the non-NULL rows, a float64 centred two-pass.  NULL where the group's second
+    central moment is 0: no row, one row, or one value."""
+    x = eval_series(call.args[0], fr)
+    valid = ~x.isna().to_numpy()
+    c = codes[valid] if len(codes) else np.zeros(int(valid.sum()), dtype=np.int64)
+    xv = x[valid].astype("float64").to_numpy(dtype=np.float64)
+    n = np.bincount(c, minlength=ng).astype(np.float64)
+
+    def by_group(v):
+        return np.bincount(c, weights=v, minlength=ng)
+
+    with np.errstate(invalid="ignore", divide="ignore"):
+        d = xv - (by_group(xv) / n)[c]
+        d = d - (by_group(d) / n)[c]  # (the rounded mean's residue)
+        m2 = by_group(d * d)
+        ok = m2 > 0
+        m2 = np.where(ok, m2, 1.0)
+        res = np.sqrt(n) * by_group(d ** 3) / (m2 * np.sqrt(m2)) if call.name == "skewness" else \
+            n * by_group(d ** 4) / (m2 * m2) - 3.0
+    return to_series(pd.Series(np.where(ok, res, np.nan)), out_t)
 
 
 def _agg_comoment(call: A.Call, fr: Frame, codes: np.ndarray, ng: int, out_t: str) -> pd.Series:

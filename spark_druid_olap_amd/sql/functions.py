@@ -115,6 +115,19 @@ def comoment_type(call: A.Call) -> str:
     return "double"
 
 
+def central_moment_type(call: A.Call) -> str:
+    """skewness / kurtosis: exactly one numeric argument, no DISTINCT; a double."""
+    n = call.name
+    if call.distinct:
+        raise AnalysisError(f"{n}(DISTINCT ...) is not supported")
+    if len(call.args) != 1:
+        raise AnalysisError(f"{n} takes exactly 1 argument, got {len(call.args)}")
+    t = typeof(call.args[0])
+    if base(t) not in INTEGRAL and base(t) not in ("double", "float", "decimal"):
+        raise AnalysisError(f"{n} over the non-numeric type {t}")
+    return "double"
+
+
 def extreme_type(call: A.Call) -> str:
     """max_by / min_by (x, y): exactly two arguments, no DISTINCT; the type of x."""
     n = call.name
@@ -215,7 +228,8 @@ def typeof(e: A.Expr) -> str:
         return "boolean"
     if isinstance(e, A.WindowExpr):
         f = e.func
-        if f.name in A.COMOMENT_FUNCS or f.name in A.EXTREME_FUNCS or f.name in A.HISTOGRAM_FUNCS:
+        if f.name in A.COMOMENT_FUNCS or f.name in A.EXTREME_FUNCS or f.name in A.HISTOGRAM_FUNCS or \
+                f.name in A.CENTRAL_MOMENT_FUNCS:
             raise AnalysisError(f"{f.name} over a window is not supported")
         if f.name in ("rank", "dense_rank", "row_number", "ntile"):
             return "int"
@@ -229,6 +243,8 @@ def typeof(e: A.Expr) -> str:
             return quantile_type(e)
         if e.name in A.COMOMENT_FUNCS:
             return comoment_type(e)
+        if e.name in A.CENTRAL_MOMENT_FUNCS:
+            return central_moment_type(e)
         if e.name in A.EXTREME_FUNCS:
             return extreme_type(e)
         if e.name in A.HISTOGRAM_FUNCS:
